@@ -124,6 +124,63 @@ def loss_fn(out, heads):
     return loss
 
 
+DUMP_BUDGET_BYTES = 64_000_000   # all files of one --dump-outputs directory, .npy headers included
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _detached(x):
+    """Detached views of every tensor in a (nested) model output; anything else is dropped."""
+    if torch.is_tensor(x):
+        return x.detach()
+    if isinstance(x, dict):
+        return {k: _detached(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_detached(v) for v in x]
+    return None
+
+
+def _named_arrays(prefix, x):
+    """Flatten a nested output into {"prefix.key.index": tensor}."""
+    if torch.is_tensor(x):
+        return {prefix: x}
+    items = x.items() if isinstance(x, dict) else enumerate(x) if isinstance(x, list) else ()
+    out = {}
+    for k, v in items:
+        out.update(_named_arrays(f"{prefix}.{k}", v))
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy: floating tensors as float32 (float64 stays float64), others as float64.  When
+    the whole exceeds DUMP_BUDGET_BYTES, every array of more than 4096 elements is replaced by a sample of its flattened
+    elements: the same fraction of each, at indices drawn (sorted, without replacement) from a generator seeded by
+    DUMP_SAMPLE_SEED and the array's name, so that two runs with the same arguments write the same elements."""
+    import zlib
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        host[name] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_BUDGET_BYTES - 256 * len(host)   # an .npy header is 128 bytes (256 for very long shapes)
+    sampled = []
+    if total > budget:
+        small = sum(a.nbytes for a in host.values() if a.size <= 4096)
+        frac = (budget - small) / (total - small)
+        for name, a in host.items():
+            if a.size > 4096:
+                rng = np.random.default_rng([DUMP_SAMPLE_SEED, zlib.crc32(name.encode())])
+                idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+                host[name] = a.reshape(-1)[idx]
+                sampled.append(name)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": len(host), "bytes": sum(a.nbytes for a in host.values()), "sampled": sampled,
+            "sample_seed": DUMP_SAMPLE_SEED if sampled else None}
+
+
 def cpu_baseline(c, sd, dd, steps, warmup, hf_body=None):
     """The oracle (CPU restatement of the reference path, pinned to the reference's outputs by the golden
     fixtures) timed on this host's cores: forward+backward, fp32, dropout 0 -- same workload, bounded sample.
@@ -420,13 +477,16 @@ def main():
     ap.add_argument("--no-live-trace", action="store_true",
                     help="skip the child rocprofv3 --kernel-trace run that times the kernels of the replayed step for `roofline`")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--min-time", type=float, default=1.0,
+    ap.add_argument("--min-time", type=float, default=0.0,
                     help="when K timed steps take < 0.5 s, repeat the K-step region until this many seconds are timed in "
-                         "total (median over repeats reported; 0 = a single K-step region)")
+                         "total (median over repeats reported; 0 = default: a single K-step region, exactly --steps timed steps)")
     ap.add_argument("--max-repeats", type=int, default=400)
     ap.add_argument("--cpu-steps", type=int, default=32, help="timed CPU-baseline steps (0 disables)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--dump-kernels", default=None, help="write the per-(entry point, shape) timing table here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (model outputs, loss, every parameter "
+                         "gradient) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (seeded samples beyond that)")
     ap.add_argument("--pmc-calibration", action="store_true",
                     help="after the profiled pass launch ONE known streaming copy (100 MiB in, 100 MiB out, 16 B / lane): "
                          "under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE its raw counters calibrate the traffic numbers")
@@ -488,6 +548,8 @@ def main():
         else:
             dist.init_process_group(backend)
     if args.config == "pool":   # segment pooling as its own workload: bench_pool.py
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the decoder step, not --config pool")
         import bench_pool
 
         def pool_barrier():
@@ -584,11 +646,16 @@ def main():
             reducer.launch(bucket_of[1 + n_layer_buckets - 1 - int(tag)])
 
     one = torch.ones((), device=dev)
+    # what the step hands its caller, kept for --dump-outputs: detached views of the outputs and the loss (under a HIP graph
+    # they are the graph's own buffers, rewritten by every replay); the gradients are read from reducer.flat
+    last = {}
 
     def fwd_bwd():
         model.zero_grad(set_to_none=True)
         out = model(dict(dd))
         loss = loss_fn(out, c["heads"])
+        if args.dump_outputs:
+            last["out"], last["loss"] = _detached({k: v for k, v in out.items() if k not in dd}), loss.detach()   # not the inputs
         if enc.grad_arena is not None:
             with ops.grad_arena(enc.grad_arena, enc.grad_arena_buffers, pack_follows=True):   # every slot offered for the whole pass
                 loss.backward(gradient=one)   # cached seed gradient: no ones_like fill in the step
@@ -757,7 +824,8 @@ def main():
     # A K-step region of a ~1.4 ms step is a few tens of ms: one clock ramp or a noisy neighbour moves it by percents and a
     # 1 Hz SMI sampler never sees the GPU busy.  When K steps take < 0.5 s the K-step region is REPEATED
     # (each repeat = exactly K steps with the same brackets) until >= args.min_time seconds are timed in total;
-    # ms_per_step = MEDIAN over the repeats, min / max beside it.  steps / warmup keep their meaning.
+    # ms_per_step = MEDIAN over the repeats, min / max beside it.  Only on request (--min-time > 0): by default the run times
+    # exactly --steps steps, one K-step region.
     dts = [timed_k_steps()]
     if dts[0] < 0.5 and args.min_time > 0:
         repeats = int(min(args.max_repeats, max(2, -(-args.min_time // dts[0]))))
@@ -786,6 +854,16 @@ def main():
         torch.distributed.all_reduce(hi, op=torch.distributed.ReduceOp.MAX)
         grads_identical = bool(torch.equal(lo, hi)) and bool(torch.isfinite(fp).all()) and bool((fp[1::2] > 0).all())
         grad_fingerprint = [[float(fp[2 * i]), float(fp[2 * i + 1])] for i in range(len(reducer.flat))]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything below runs the model again
+        names = {id(p): n for n, p in model.named_parameters()}
+        grads = {}
+        for flat, bucket in zip(reducer.flat, reducer.buckets):
+            off = 0
+            for p in bucket:
+                grads["grad." + names[id(p)]] = flat[off:off + p.numel()].view(p.shape)
+                off += p.numel()
+        dumped = dump_outputs(args.dump_outputs, {**_named_arrays("out", last["out"]), "loss": last["loss"], **grads})
 
     result = None
     if rank == 0:
@@ -1059,6 +1137,8 @@ def main():
                 result["cpu_baseline"]["sample"] += "; caption body = stock HF T5 on the CPU (third-party, as the reference calls it)"
             result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
         result["chain_error"] = chain_err or bool(_ops.chain_error(dev))   # (the side legs above replay chain launches too)
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         print(json.dumps(result))
     if dist_on:
         torch.distributed.barrier()

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Executed by tests/test_dropin_registry.py in a process of its own (build container only: imports /root/reference).
+"""Run by hand where the reference is importable (python tests/dropin_registry_check.py; prints DROPIN-OK): not part of the
+suite, which runs from this repository alone.
 
 INTEGRATION.md section 1, executed: the HIP modules are registered into the REFERENCE'S OWN registries
 (modules/build.py:6-9) under the names a maintainer's YAML would select, and the REFERENCE'S Query3DUnified

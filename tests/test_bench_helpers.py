@@ -51,3 +51,29 @@ def test_committed_profiles_are_tied_to_the_build(tmp_path, monkeypatch):
     assert any("pmc_mfma_r06_c2.json" in r for r in info["refused"])
     pmc2, _m, stats2, info2 = bench.committed_profiles("c2", bench.DEFAULT_COMPUTE, bad)
     assert pmc2 is None and stats2 == {} and len(info2["refused"]) >= 2
+
+
+def test_dump_outputs_is_deterministic_typed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files, the same bytes from run to run, full arrays under the budget and seeded
+    samples (the same elements every run) once the whole would exceed it."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    arrays = {"out.query_embeds": torch.randn(8, 100, 256, generator=g).bfloat16(), "loss": torch.tensor(1.5, dtype=torch.float64),
+              "out.label": torch.arange(10), "grad.w": torch.randn(1000, 1000, generator=g)}
+    r = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert r["arrays"] == 4 and r["sampled"] == []
+    q = np.load(tmp_path / "full" / "out.query_embeds.npy")
+    assert q.dtype == np.float32 and q.shape == (8, 100, 256) and np.array_equal(q, arrays["out.query_embeds"].float().numpy())
+    assert np.load(tmp_path / "full" / "loss.npy").dtype == np.float64
+    assert np.load(tmp_path / "full" / "out.label.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1_000_000)
+    for d in ("a", "b"):
+        r = bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(r["sampled"]) == ["grad.w", "out.query_embeds"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 1_000_000
+    for f in (tmp_path / "a").iterdir():
+        a, b = np.load(f), np.load(tmp_path / "b" / f.name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f.name
+    w = np.load(tmp_path / "a" / "grad.w.npy")
+    assert 0 < w.size < 1_000_000 and np.isin(w, arrays["grad.w"].numpy()).all()

@@ -18,6 +18,9 @@ def test_model_fixture(name):
     assert abs(synth.state_checksum(sd) - float(z["meta/weights_checksum"])) < 1e-6 * float(z["meta/weights_checksum"]), \
         "synthetic weight generator drifted from the one that produced the fixtures"
     grads = any(k.startswith("grad/") for k in z.files)
+    if args.get("float64"):   # the fixture holds the reference's fp64 run (make_golden.run_model_case): the oracle runs in fp64 too
+        sd = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in sd.items()}
+        dd = {k: (v.double() if torch.is_tensor(v) and v.dtype == torch.float32 else v) for k, v in dd.items()}
     out, collect, loss, g = util.run_oracle(args, sd, dd, grads=grads)
     for i, q in enumerate(collect):
         util.check_against(z, f"layer_query/{i}", q, **TOL)

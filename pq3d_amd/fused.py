@@ -19,84 +19,18 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional
 
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from . import ops
+from . import ops, wgrad
+from .wgrad import _colsum_acc  # noqa: F401  (importable from fused as before: tests/test_gpu_ops.py)
 from ._lib import BF16
 from .profiler import timed
 
 MAXG = L.MAXG
-
-
-def _chunks(seq, n):
-    for i in range(0, len(seq), n):
-        yield seq[i:i + n]
-
-
-def _gemm_groups(n_per_call_limit, **kw):
-    """L.gemm over arbitrarily many groups (split into calls of <= limit groups; kconcat chains handled by caller)."""
-    L.gemm(**kw)
-
-
-def _colsum_acc(xs: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], rows: int) -> None:
-    """outs[g] += column sums of xs[g] viewed as [rows, N] (bias gradients into the arena)."""
-    N = xs[0].numel() // rows
-    # operands of one output that lie back to back in memory (the mask head's calls write slices of one buffer) are one taller
-    # operand: (first tensor, output, number of row blocks)
-    merged = []
-    for xt, ot in zip(xs, outs):
-        if merged and merged[-1][1].data_ptr() == ot.data_ptr() and xt.dtype == merged[-1][0].dtype and \
-                xt.data_ptr() == merged[-1][0].data_ptr() + merged[-1][2] * rows * N * xt.element_size():
-            merged[-1][2] += 1
-        else:
-            merged.append([xt, ot, 1])
-    for nblk in sorted({m_[2] for m_ in merged}):
-        # a launch adds with one (non-atomic) writer per output element: outputs must be unique within a launch
-        # (shared weights across num_blocks put the same bias slice in several groups) -> greedy batching
-        batches, cur, seen = [], ([], []), set()
-        for xt, ot, nb_ in merged:
-            if nb_ != nblk:
-                continue
-            if ot.data_ptr() in seen or len(cur[0]) == MAXG:
-                batches.append(cur)
-                cur, seen = ([], []), set()
-            cur[0].append(xt); cur[1].append(ot); seen.add(ot.data_ptr())
-        batches.append(cur)
-        for xc, oc in batches:
-            xa = (C.c_void_p * len(xc))(*[L.ptr(t) for t in xc])
-            oa = (C.c_void_p * len(oc))(*[L.ptr(t) for t in oc])
-            # accumulate = 2: the one-writer (bit-reproducible) form at every row count; 1 lets long columns add row slices atomically
-            L.check(L.lib().pq3d_colsum_grouped(xa, oa, len(xc), L.dt_of(xc[0]), rows * nblk, N, N, 2 if ops.DETERMINISTIC else 1,
-                                                L.stream()), "pq3d_colsum_grouped")
-
-
-def _splitk(tiles: int, k: int, ct: int, groups: int) -> int:
-    nkt = max(1, k // (64 if ct == BF16 else 32))
-    return max(1, min(nkt // 2 if nkt >= 2 else 1, max(1, 768 // max(tiles * groups, 1)), 64))
-
-
-def _dw_acc(gs, xs, x2s, outs, ct, bias_outs=None):
-    """outs[g][N,K] += gs[g]^T @ (xs[g] + x2s[g])  (grouped split-K, accumulating atomics) and, fused into the same
-    launch, bias_outs[g][N] += column sums of gs[g] (the bias gradient of the same linear layer)."""
-    N, K = outs[0].shape
-    R = gs[0].numel() // N
-    tiles = ((N + 63) // 64) * ((K + 63) // 64)
-    epl = 8 if ct == BF16 else 4
-    fusable = bias_outs is not None and N % epl == 0 and K % epl == 0 and N >= epl and K >= epl and \
-        all(t.data_ptr() % 16 == 0 for t in list(gs) + list(xs))
-    gs, xs, x2s = ops.dw_operands(gs, xs, x2s, N, K, R, ct)   # long reductions: bf16 operands once, 128 x 128 tiles
-    for i in range(0, len(gs), MAXG):
-        g_, x_, o_ = gs[i:i + MAXG], xs[i:i + MAXG], outs[i:i + MAXG]
-        x2_ = x2s[i:i + MAXG] if x2s is not None else None
-        L.gemm(M=N, N=K, K=R, A=g_, B=x_, B2=x2_, Cs=o_, ct=ct, lda=N, ldb=K, ldc=K, transA=True, transB=True,
-               splitk=max(2, _splitk(tiles, R, ct, len(g_))), accumulate=True,
-               colsum=bias_outs[i:i + MAXG] if fusable else None)
-    if bias_outs is not None and not fusable:
-        _colsum_acc(gs, bias_outs, R)
 
 
 # one-launch row-local chain (csrc/chain_ffn.hip) for the forward's out-projection + LayerNorm + FFN + LayerNorm; PQ3D_CHAIN=0 or
@@ -112,42 +46,6 @@ def set_chain(on: bool) -> None:
 def _chain_on(dev) -> bool:
     """Chains requested AND valid on this device (ops.chain_device_ok: MI355X in SPX mode, round-robin workgroup -> XCD placement measured)."""
     return _CHAIN and ops.chain_device_ok(dev)
-
-
-class _DwQueue:
-    """Deferred weight-gradient GEMMs.  Every dW = g^T (x [+ x2]) of the backward pass only feeds the gradient arena,
-    so they are queued and flushed at the end as a few grouped launches per (shape, dtype) bucket instead of one
-    launch per linear layer (c2: 41 launches -> 6)."""
-
-    def __init__(self, ct):
-        self.ct, self.buckets = ct, {}
-
-    def add(self, gs, xs, x2s, outs, ct=None, bias_outs=None):
-        for i in range(len(gs)):
-            N, K = outs[i].shape
-            key = (N, K, gs[i].numel() // N, gs[i].dtype, xs[i].dtype, bias_outs is not None)
-            b = self.buckets.setdefault(key, ([], [], [], [], []))
-            b[0].append(gs[i]); b[1].append(xs[i]); b[2].append(x2s[i] if x2s is not None else None)
-            b[3].append(outs[i]); b[4].append(bias_outs[i] if bias_outs is not None else None)
-
-    def flush(self):
-        # (forking the buckets over 3 / 5 streams -- parallel branches of the captured graph -- was measured at config 2:
-        # 1.50 -> 1.80 / 2.17 ms; branch joins cost far more than the overlapped tails save)
-        multi, rest = [], {}
-        for key, (g, x, x2, o, bo) in self.buckets.items():
-            N, K, R = key[0], key[1], key[2]
-            if self.ct == BF16 and not ops.dw_long_path(N, K, R, len(g), self.ct) and \
-                    all(ops.tt_multi_ok(g[i], x[i], x2[i], o[i], bo[i], N, K, R) for i in range(len(g))):
-                multi += list(zip(g, x, x2, o, bo))
-            else:
-                rest[key] = (g, x, x2, o, bo)
-        if multi and ops.tt_multi_pays(multi):   # every short-reduction weight / bias gradient of the flush: ONE launch
-            ops.tt_multi(multi)                  # (csrc/gemm_ttmulti.hip)
-        else:
-            rest = self.buckets
-        for key, (g, x, x2, o, bo) in rest.items():
-            _dw_acc(g, x, x2 if any(t is not None for t in x2) else None, o, self.ct, bo if key[5] else None)
-        self.buckets = {}
 
 
 class FusedSpec:
@@ -362,7 +260,7 @@ class _DecoderBackward:
         self.dcls, self.dmlog = list(dheads[:n_mh]), list(dheads[n_mh:2 * n_mh])
         self.n_app = n_app = len(self.tape)
         self._open_arena()   # self.gv (parameter -> gradient view), self.accumulate, self.in_place, self.dxr_zero
-        self.dwq = _DwQueue(ct)
+        self.dwq = wgrad.Queue(split_x2=False)
         self.sb_queue = []   # (W, b, d bias, dW, db) of every spatial self-attention application
         self.dqpos_parts: List[torch.Tensor] = []
         self.dKV = torch.empty(n_app, 2, M, B, Ns, d, dtype=self.ad, device=dev)
@@ -374,7 +272,7 @@ class _DecoderBackward:
         self.per_layer = bool(getattr(enc, "grad_bucket_per_layer", False)) and ready_cb is not None
         if ready_cb is not None:
             def ready(tag):
-                # weight gradients queued by ops.linear layers that ran backward BEFORE the decoder (heads; ops._DwDeferred)
+                # weight gradients queued by ops.linear layers that ran backward BEFORE the decoder (heads)
                 # must be in their slots before an owner is told that a bucket is final
                 ops.dw_deferred_flush()
                 ready_cb(tag)

@@ -12,14 +12,12 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from . import wgrad
+from .wgrad import dw_long_path, tt_multi, tt_multi_ok  # noqa: F401  (the weight-gradient helpers, importable from ops as before)
 from ._lib import BF16, BF16X3, F32
 from .profiler import timed
 
 _empty = torch.empty
-# PQ3D_DETERMINISTIC=1: reductions that have an order-independent form take it (today: bias-gradient column sums of long
-# accumulating calls, include/pq3d_hip.h pq3d_colsum_grouped accumulate == 2).  Split-K weight gradients and the LayerNorm
-# parameter gradients still add with fp32 atomics.
-DETERMINISTIC = os.environ.get("PQ3D_DETERMINISTIC", "0") == "1"
 
 
 def act_dtype(ct: int) -> torch.dtype:
@@ -49,11 +47,6 @@ def sa_ct(ct: int) -> int:
 
 def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if t is None else t.contiguous()
-
-
-def _splitk(tiles: int, k: int, ct: int) -> int:
-    nkt = max(1, k // (64 if ct == BF16 else 32))
-    return max(1, min(nkt // 2 if nkt >= 2 else 1, 512 // max(tiles, 1), 64))
 
 
 # ------------------------------------------------------------------------------------------------ dropout
@@ -422,21 +415,14 @@ def mean_all(x: torch.Tensor) -> torch.Tensor:
 # gradient buffer, so nothing waits for it: the products are queued per (shape, dtype) bucket and launched as a few GROUPED
 # split-K launches when the pass ends (grad_arena.__exit__) instead of one launch per layer -- the caption body's 46 launches of
 # [512 x 512] / [2048 x 512] products over 512 rows at config 5 are latency chains of ~15 us each.  The decoder's own backward
-# has done the same for its layers since round 1 (fused._DwQueue); this is the same idea for everything that goes through
-# ops.linear / ops.linear_group around it.
-class _DwDeferred:
-    buckets = {}     # (N, K, R, g dtype, x dtype, has x2, has bias, ct) -> lists
-    nbytes = 0       # operand bytes the queue keeps alive; above _DW_DEFER_CAP the queue is flushed on the spot
-
-
-_DW_DEFER_CAP = 256 << 20   # the deferral exists for the latency-bound small-R products; big operands are not held for long
-
-
-_DW_DEFER = True    # module switch for A/B measurements (tools/probes/bench_nodefer.py)
+# does the same for its layers with a queue of its own; this one serves everything that goes through ops.linear /
+# ops.linear_group around it.
+_DW_QUEUE = wgrad.Queue(split_x2=True)
+_DW_QUEUE_CAP = 256 << 20   # the deferral exists for the latency-bound small-R products; big operands are not held for long
 
 
 def _dw_can_defer(g, x, x2, N, K) -> bool:
-    if not _DW_DEFER or not _Arena.whole_pass or _Arena.mode is None:
+    if not _Arena.whole_pass or _Arena.mode is None:
         return False
     return not ((x2 is not None and (x2.dtype != torch.float32 or x.dtype != torch.float32)) or N % 8 or K % 8 or
                 g.data_ptr() % 16 or x.data_ptr() % 16 or (x2 is not None and x2.data_ptr() % 16) or
@@ -472,110 +458,25 @@ def _param_has_hooks(q) -> bool:
         return False
 
 
-def _dw_defer(g, x, x2, dw, db, N, K, R, ct, pptrs=()) -> bool:
+def _dw_defer(g, x, x2, dw, db, N, K, ct, pptrs=()) -> bool:
     """Queue dw[N, K] += g^T (x [+ x2]) (and db[N] += column sums of g); False when the pass has no whole-pass arena.
     A parameter with Python-visible gradient hooks, or one listed through dw_defer_exclude (torch DDP: its C++ bucket hooks are
     invisible from Python), is never deferred: its hook would read the slot before the queued product has run."""
     if not _dw_can_defer(g, x, x2, N, K) or any(_param_has_hooks(q) for q in pptrs if q is not None):
         return False
-    _DwDeferred.nbytes += g.numel() * g.element_size() + x.numel() * x.element_size() + \
-        (x2.numel() * x2.element_size() if x2 is not None else 0)
-    key = (N, K, R, g.dtype, x.dtype, x2 is not None, db is not None, ct)
-    b = _DwDeferred.buckets.setdefault(key, ([], [], [], [], []))
     # the queue keeps its OWN view objects of the slots: AccumulateGrad adopts the returned gradient without a copy only when
     # nobody else references that tensor object (arena_take) -- a second reference would turn .grad into a clone of zeros
-    b[0].append(g); b[1].append(x); b[2].append(x2); b[3].append(dw.view(N, K)); b[4].append(db.view(-1) if db is not None else None)
-    if _DwDeferred.nbytes > _DW_DEFER_CAP:
+    _DW_QUEUE.add([g], [x], [x2], [dw.view(N, K)], ct, [db.view(-1)] if db is not None else None)
+    if _DW_QUEUE.nbytes > _DW_QUEUE_CAP:
         dw_deferred_flush()
     return True
-
-
-_TT_MULTI = os.environ.get("PQ3D_TT_MULTI", "1") != "0"   # A/B switch (tools/probes): one launch for a whole flush
-# ... also for long reductions over few tiles (the encoders' [256 x 256] over 8192 rows)?  Measured slower (k-slices x 256 x 128
-# tiles = 3x the atomics of the 64 x 64 split: c4 +1.0 %, c2 +0.2 .. 1.7 % on the same box): off
-_TT_LONG = os.environ.get("PQ3D_TT_MULTI_LONG", "0") != "0"
-
-
-def dw_long_path(N: int, K: int, R: int, count: int, ct: int) -> bool:
-    """dw_operands' condition: a LONG reduction with enough 128 x 128 output tiles to fill the chip -> operands rounded to bf16
-    once, then the 128 x 128-tile bf16 kernel (gemm_tt128).  Everything else is pq3d_gemm_tt_multi's."""
-    return ct == BF16 and R >= 2048 and R % 64 == 0 and N % 128 == 0 and K % 128 == 0 and (N // 128) * (K // 128) * count >= 64
-
-
-def tt_multi_ok(g, x, x2, dw, db, N: int, K: int, R: int) -> bool:
-    """Can dW[N, K] += g^T (x [+ x2]) (+ db[N] += colsum g) join the one-launch flush (pq3d_gemm_tt_multi)?  (Callers keep long
-    reductions over many tiles -- dw_long_path -- on the 128 x 128-tile bf16 kernel.)"""
-    if not _TT_MULTI or (R >= 2048 and not _TT_LONG) or R < 1 or N % 8 or K % 8 or N < 8 or K < 8 or R * max(N, K) >= (1 << 31):
-        return False
-    for t in (g, x):
-        if t.dtype not in (torch.float32, torch.bfloat16) or not t.is_contiguous() or t.data_ptr() % 16:
-            return False
-    if x2 is not None and (x2.dtype != torch.float32 or x.dtype != torch.float32 or not x2.is_contiguous() or x2.data_ptr() % 16):
-        return False
-    if dw.dtype != torch.float32 or not dw.is_contiguous() or (db is not None and (db.dtype != torch.float32 or not db.is_contiguous())):
-        return False
-    return g.numel() == R * N and x.numel() == R * K
-
-
-def tt_multi_pays(problems) -> bool:
-    """The one-launch flush wins through its 256 x 128 tiles (2.5-3x fewer operand re-reads from L2) while those fit about one
-    round of workgroups (<= 400 wide tiles: the decoder's flush at configs 2 / 4 / 5); a flush WITHOUT such a launch -- the
-    caption body's ~660 wide tiles over 512 rows, which the library sends back to 64 x 64 tiles -- is faster as one
-    gemm_wktt launch per (shape, dtype) bucket (config 5, same box: 6.21 vs 6.27 ms per step)."""
-    wt = sum((dw.shape[-2] // 256) * (dw.shape[-1] // 128) for _g, _x, _x2, dw, _db in problems
-             if dw.shape[-2] % 256 == 0 and dw.shape[-1] % 128 == 0)
-    return 0 < wt <= 400
-
-
-def tt_multi(problems) -> None:
-    """problems: [(g [R,N], x [R,K], x2 or None, dw [N,K], db [N] or None)] -- every weight (and bias) gradient of a flush in
-    ONE launch per 56 problems (csrc/gemm_ttmulti.hip) instead of one launch per (shape, dtype) bucket."""
-    for s0 in range(0, len(problems), L.TT_MAX_PROBLEMS):
-        ch = problems[s0:s0 + L.TT_MAX_PROBLEMS]
-        arr = (L.TtProblem * len(ch))()
-        fl = nb = 0.0
-        for q, (g, x, x2, dw, db) in zip(arr, ch):
-            N, K = dw.shape[-2], dw.shape[-1]
-            R = g.numel() // N
-            q.M, q.N, q.K, q.lda, q.ldb = N, K, R, N, K
-            q.dtA, q.dtB = L.dt_of(g), L.dt_of(x)
-            q.A, q.B, q.B2, q.C, q.colsum = L.ptr(g), L.ptr(x), L.ptr(x2), L.ptr(dw), L.ptr(db)
-            fl += 2.0 * N * K * R
-            nb += float(g.numel() * g.element_size() + x.numel() * x.element_size() + (x2.numel() * x2.element_size() if x2 is not None else 0)
-                        + N * K * 4 + (N * 4 if db is not None else 0))   # compulsory: both operands once, the fp32 result (+ bias gradient)
-        L.check(timed("pq3d_gemm_tt_multi", f"ttmulti{len(ch)}", fl, nb, L.lib().pq3d_gemm_tt_multi, arr, len(ch), L.stream()),
-                "pq3d_gemm_tt_multi")
 
 
 def dw_deferred_flush(run: bool = True) -> None:
     """Launch (run=False: drop) the queued weight-gradient products.  Called when the pass ends (grad_arena.__exit__), from
     the fused decoder's readiness reports, from FlatGradAllReducer.launch() / pack() -- no reader of a slot gets ahead of the
-    queue -- and when the queue holds more than _DW_DEFER_CAP bytes of operands."""
-    buckets, _DwDeferred.buckets, _DwDeferred.nbytes = _DwDeferred.buckets, {}, 0
-    if not run:
-        return
-    multi, rest = [], {}
-    for key, (gs, xs, x2s, dws, dbs) in buckets.items():
-        N, K, R, ct = key[0], key[1], key[2], key[7]
-        if ct == BF16 and not dw_long_path(N, K, R, len(gs), ct) and \
-                all(tt_multi_ok(g, x, x2, dw, db, N, K, R) for g, x, x2, dw, db in zip(gs, xs, x2s, dws, dbs)):
-            multi += list(zip(gs, xs, x2s, dws, dbs))
-        else:
-            rest[key] = (gs, xs, x2s, dws, dbs)
-    if multi and tt_multi_pays(multi):
-        tt_multi(multi)
-    else:
-        rest = buckets
-    for (N, K, R, _gd, _xd, has2, hasb, ct), (gs, xs, x2s, dws, dbs) in rest.items():
-        tiles = ((N + 63) // 64) * ((K + 63) // 64)
-        ga, xa, x2a = dw_operands(gs, xs, x2s if has2 else None, N, K, R, ct)
-        for i in range(0, len(ga), L.MAXG):
-            n = len(ga[i:i + L.MAXG])
-            nkt = max(1, R // (64 if ct == BF16 else 32))
-            sk = max(1, min(nkt // 2 if nkt >= 2 else 1, max(1, 768 // max(tiles * n, 1)), 64))
-            L.gemm(M=N, N=K, K=R, A=ga[i:i + L.MAXG], B=xa[i:i + L.MAXG], B2=x2a[i:i + L.MAXG] if x2a is not None else None,
-                   Cs=dws[i:i + L.MAXG], ct=ct, lda=N, ldb=K, ldc=K, transA=True, transB=True, splitk=max(2, sk),
-                   accumulate=True, colsum=dbs[i:i + L.MAXG] if hasb else None)
+    queue -- and when the queue holds more than _DW_QUEUE_CAP bytes of operands."""
+    _DW_QUEUE.flush(run)
 
 
 class _Linear(Function):
@@ -631,7 +532,8 @@ class _Linear(Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
             dx = _empty(x.shape, dtype=x.dtype, device=x.device)
             # a long reduction over few output tiles (LM head: 512 x 512 outputs, N = 32128) is split over K
-            sk = _splitk(((R + 63) // 64) * ((K + 63) // 64), N, ct) if (dx.dtype == torch.float32 and N >= 8192) else 1
+            sk = wgrad.splitk(((R + 63) // 64) * ((K + 63) // 64), N, ct, wgrad.SPLITK_CAP_LAYER) \
+                if (dx.dtype == torch.float32 and N >= 8192) else 1
             if sk > 1:   # these shapes run on gemm_wk's 64 x 256 tiles: one round of workgroups over the chip (c5's LM head: 8 -> 16
                 sk = max(sk, min(64, 256 // max(1, ((R + 63) // 64) * ((K + 255) // 256))))   # slices, 107 -> 81 us)
             L.gemm(M=R, N=K, K=N, A=[g], B=[w], Cs=[dx], ct=ct, lda=N, ldb=K, ldc=K, transB=True, splitk=sk, alpha=alpha)
@@ -641,30 +543,21 @@ class _Linear(Function):
         want_db = ctx.has_b and ctx.needs_input_grad[2]
         give_w = True
         if ctx.needs_input_grad[1]:
-            tiles = ((N + 63) // 64) * ((K + 63) // 64)
-            epl = 8 if ct == BF16 else 4
-            # the bias gradient rides on the weight-gradient GEMM when its fast (aligned) path applies
-            fuse = want_db and N % epl == 0 and K % epl == 0 and N >= epl and K >= epl and \
-                g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and (x2 is None or x2.dtype == torch.float32) and \
-                (x2 is None or x.dtype == torch.float32)
+            fuse = want_db and wgrad.colsum_fusable([g], [x], [x2], N, K, ct)   # the bias gradient rides on the same launch
             # the owner's gradient arena, when offered for this pass: accumulate straight into the slots (pre-zeroed)
             slot, give = arena_take([ctx.pptr[0]] + ([ctx.pptr[1]] if fuse else []), [N * K] + ([N] if fuse else []))
             if slot is not None:
                 dw, give_w = slot[0].view(N, K), give
                 if fuse:
                     db = slot[1]
-                if not (alpha == 1.0 and _dw_defer(g, x, x2, dw, db if fuse else None, N, K, R, ct, pptrs=ctx.pptr)):   # else: queued until the pass ends
-                    ga, xa, x2a = dw_operands([g], [x], [x2], N, K, R, ct)   # long reductions: bf16 operands, 128 x 128 tiles
-                    L.gemm(M=N, N=K, K=R, A=ga, B=xa, B2=x2a, Cs=[dw], ct=ct, lda=N, ldb=K, ldc=K, transA=True, transB=True,
-                           splitk=max(2, _splitk(tiles, R, ct)), colsum=[db] if fuse else None, accumulate=True, alpha=alpha)
+                if not (alpha == 1.0 and _dw_defer(g, x, x2, dw, db if fuse else None, N, K, ct, pptrs=ctx.pptr)):   # else: queued until the pass ends
+                    wgrad.launch([g], [x], [x2], [dw], [db] if fuse else None, ct, wgrad.SPLITK_CAP_LAYER, alpha=alpha)
             else:
-                ga, xa, x2a = dw_operands([g], [x], [x2], N, K, R, ct)   # long reductions: bf16 operands, 128 x 128 tiles
                 dw = _empty(N, K, dtype=torch.float32, device=x.device)
                 if fuse:
                     db = _empty(N, dtype=torch.float32, device=x.device)
-                L.gemm(M=N, N=K, K=R, A=ga, B=xa, B2=x2a, Cs=[dw], ct=ct, lda=N, ldb=K, ldc=K, transA=True,
-                       transB=True, splitk=max(2, _splitk(tiles, R, ct)) if fuse else _splitk(tiles, R, ct),
-                       colsum=[db] if fuse else None, alpha=alpha)
+                wgrad.launch([g], [x], [x2], [dw], [db] if fuse else None, ct, wgrad.SPLITK_CAP_LAYER, min2=fuse, accumulate=False,
+                             alpha=alpha)
         if want_db and db is None:
             db = colsum(g.view(R, N))
         dres = dy.contiguous() if (ctx.has_res and ctx.needs_input_grad[11]) else None
@@ -673,49 +566,6 @@ class _Linear(Function):
             if db is not None and want_db and fuse:
                 db = None
         return dx, dw, db, dx2, None, None, None, None, None, None, None, dres, None
-
-
-def dw_operands(gs, xs, x2s, N: int, K: int, R: int, ct: int):
-    """Operands of weight-gradient products dW[N, K] += g^T (x [+ x2]) over a LONG reduction (R >= 2048 rows: the encoders'
-    B * N_seg rows, every projection of the stage-2 shipped shape with its 128 x 80 object rows): fp32 operands are rounded to
-    bf16 ONCE by one launch per operand shape -- the rounding the GEMM staging applies anyway, (x + x2) summed in fp32 first
-    -- so that the product takes the 128 x 128-tile bf16 kernel (gemm_tt128_kernel: half the operand re-reads of the 64 x 64
-    tile, 2 B per element instead of 4; config s2: 155 -> ~490 TFLOP/s on these launches).  Returns (gs, xs, x2s)."""
-    # ... when the launch has enough 128 x 128 output tiles to fill the chip without a deep split-K (config 2's input
-    # encoders: 3 groups of [256, 256] over 8192 rows = 12 tiles -- 14 us of rounding + 33 us against 29 us on the 64 x 64
-    # chunk kernel, measured; config s2: 16-24 groups of [768, 768] = 576+ tiles)
-    if ct != BF16 or R < 2048 or R % 64 or N % 128 or K % 128 or (N // 128) * (K // 128) * len(gs) < 64:
-        return gs, xs, x2s
-    x2s = list(x2s) if x2s is not None else [None] * len(xs)
-    if all(t.dtype == torch.bfloat16 for t in list(gs) + list(xs)) and all(t is None for t in x2s):
-        return gs, xs, None
-    if any(t.dtype != torch.float32 for t in x2s if t is not None) or \
-            any(t.dtype == torch.bfloat16 and t2 is not None for t, t2 in zip(xs, x2s)):
-        return gs, xs, (x2s if any(t is not None for t in x2s) else None)
-    cache, jobs = {}, {}
-
-    def conv(t, t2):
-        if t.dtype == torch.bfloat16:
-            return t
-        key = (t.data_ptr(), t2.data_ptr() if t2 is not None else 0, t.numel())
-        o = cache.get(key)
-        if o is None:
-            if t.numel() % 8 or t.data_ptr() % 16 or (t2 is not None and t2.data_ptr() % 16) or not t.is_contiguous():
-                return None
-            o = cache[key] = torch.empty(t.shape, dtype=torch.bfloat16, device=t.device)
-            jobs.setdefault(t.numel(), []).append((t, t2, o))
-        return o
-    g2 = [conv(t, None) for t in gs]
-    x2 = [conv(t, t2) for t, t2 in zip(xs, x2s)]
-    if any(t is None for t in g2 + x2):
-        return gs, xs, (x2s if any(t is not None for t in x2s) else None)
-    arr = lambda ts: (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
-    for n, lst in jobs.items():
-        for s0 in range(0, len(lst), L.MAXG):
-            ch = lst[s0:s0 + L.MAXG]
-            L.check(L.lib().pq3d_add_cast(arr([a for a, _, _ in ch]), arr([b for _, b, _ in ch]), arr([o for _, _, o in ch]),
-                                          len(ch), L.BF16, n, L.stream()), "pq3d_add_cast")
-    return g2, x2, None
 
 
 def linear(x, w, b=None, *, ct: int, x2=None, act: Optional[str] = None, out_dtype=torch.float32, row_mask=None,
@@ -787,17 +637,12 @@ class _LinearGroup(Function):
             give = True
             dWb = torch.zeros(G, N, K, dtype=torch.float32, device=dev)
             dWs = [dWb[g] for g in range(G)]
-        tiles = ((N + 63) // 64) * ((K + 63) // 64)
         if slot is not None and all(_dw_can_defer(gs[g], xs[g], None, N, K) for g in range(G)) and \
                 not any(_param_has_hooks(q) for q in ctx.pptr):
             for g in range(G):
-                _dw_defer(gs[g], xs[g], None, dWs[g], None, N, K, R, ct)
+                _dw_defer(gs[g], xs[g], None, dWs[g], None, N, K, ct)
             return (None, None, None, *dxs, *(dWs if give else [None] * G))   # queued until the pass ends
-        gs, xs_, _ = dw_operands(list(gs), list(xs), None, N, K, R, ct)
-        for s in range(0, G, L.MAXG):
-            e = min(G, s + L.MAXG)
-            L.gemm(M=N, N=K, K=R, A=gs[s:e], B=list(xs_[s:e]), Cs=dWs[s:e], ct=ct, lda=N, ldb=K, ldc=K,
-                   transA=True, transB=True, splitk=max(2, _splitk(tiles * (e - s), R, ct)), accumulate=True)
+        wgrad.launch(list(gs), list(xs), None, dWs, None, ct, wgrad.SPLITK_CAP_LAYER)
         return (None, None, None, *dxs, *(dWs if give else [None] * G))
 
 
@@ -1291,9 +1136,7 @@ class _LinearLNGroup(Function):
         # every atomics target of this backward (LayerNorm parameter gradients, split-K weight gradients, bias column
         # sums): the parameters' slots of the owner's gradient arena when the decoder's backward offered them for this
         # pass (zeroed by its one launch: no fill here, no pack copy later), else ONE zero-filled buffer of our own
-        tiles = ((N + 63) // 64) * ((K + 63) // 64)
-        epl = 8 if ct == BF16 else 4
-        fuse = N % epl == 0 and K % epl == 0 and all(x.data_ptr() % 16 == 0 for x in xs)
+        fuse = wgrad.colsum_fusable(list(dlin), xs, None, N, K, ct)
         slot, give = arena_take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
         if slot is not None:
             dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
@@ -1312,16 +1155,13 @@ class _LinearLNGroup(Function):
             d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dlin[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
         L.check(timed("pq3d_add_ln_bwd", f"R{R}d{N}M{G}i", 0.0, 3.0 * G * R * N * 4, L.lib().pq3d_add_ln_bwd, C.byref(d),
                       L.stream()), "pq3d_add_ln_bwd")
-        if fuse and ct == BF16 and not dw_long_path(N, K, R, G, ct) and \
-                all(tt_multi_ok(dlin[g], xs[g], None, dWs[g], dbl[g], N, K, R) for g in range(G)):
-            # short reductions only (tt_multi_ok refuses R >= 2048 unless PQ3D_TT_MULTI_LONG=1: config 2's 3 encoders of [256 x 256]
-            # over 8192 rows were measured slower on wide tiles + k-slices): the encoders of small batches / short memories --
-            # one launch with the fused bias gradient (tests/test_gpu_ops.py::test_linear_ln_group_backward_tt_multi_path)
-            tt_multi([(dlin[g], xs[g], None, dWs[g], dbl[g]) for g in range(G)])
+        probs = [(dlin[g], xs[g], None, dWs[g], dbl[g]) for g in range(G)]
+        if fuse and wgrad.tt_multi_fits(probs, N, K, R, ct):
+            # short reductions only: the encoders of small batches / short memories -- one launch with the fused bias gradient,
+            # without the tt_multi_pays check of a queue flush (tests/test_gpu_ops.py::test_linear_ln_group_backward_tt_multi_path)
+            wgrad.tt_multi(probs)
         else:
-            ga_, xa_, _ = dw_operands([dlin[g] for g in range(G)], list(xs), None, N, K, R, ct)
-            L.gemm(M=N, N=K, K=R, A=ga_, B=xa_, Cs=dWs, ct=ct, lda=N, ldb=K, ldc=K, transA=True,
-                   transB=True, splitk=max(2, _splitk(tiles * G, R, ct)), colsum=dbl if fuse else None, accumulate=True)
+            wgrad.launch([dlin[g] for g in range(G)], list(xs), None, dWs, dbl if fuse else None, ct, wgrad.SPLITK_CAP_LAYER)
         if not fuse:
             dbl = [colsum(dlin[g].view(R, N)) for g in range(G)]
         dxs = [None] * G
@@ -1433,9 +1273,9 @@ class grad_arena:
     accumulates in place.  Without this context the decoder's backward makes the offer itself (arena_offer), which only
     reaches the functions that run after it.
 
-    .grad IS NOT FINAL UNTIL THE CONTEXT EXITS: weight gradients of arena-aware linear layers are queued (_DwDeferred) and
+    .grad IS NOT FINAL UNTIL THE CONTEXT EXITS: weight gradients of arena-aware linear layers are queued (_DW_QUEUE) and
     launched grouped at __exit__ (earlier only at the fused decoder's readiness reports, FlatGradAllReducer.launch() /
-    pack(), or when the queue exceeds _DW_DEFER_CAP); a reader of p.grad inside the pass sees zeros or partial sums.
+    pack(), or when the queue exceeds _DW_QUEUE_CAP); a reader of p.grad inside the pass sees zeros or partial sums.
     Parameters with gradient hooks registered are excluded from the deferral for that reason."""
 
     def __init__(self, slots, buffers, pack_follows: bool = False):

@@ -155,7 +155,7 @@ class FlatGradAllReducer:
         prezeroed = set()
         if self.flat and self.flat[0].is_cuda:
             from . import ops
-            ops.dw_deferred_flush()   # no reader of the slots gets ahead of queued weight-gradient products (ops._DwDeferred)
+            ops.dw_deferred_flush()   # no reader of the slots gets ahead of queued weight-gradient products
             prezeroed = ops.arena_zeroed_buffers()   # buffers a whole-pass gradient arena zero-filled for this very pass
         for bi, (flat, bucket) in enumerate(zip(self.flat, self.buckets)):
             if buckets is not None and bi not in buckets:
@@ -256,7 +256,7 @@ class FlatGradAllReducer:
             return
         if self.flat[bi].is_cuda:
             from . import ops
-            ops.dw_deferred_flush()   # weight gradients still queued for this pass (ops._DwDeferred) land before the bucket leaves
+            ops.dw_deferred_flush()   # weight gradients still queued for this pass land before the bucket leaves
         cur = torch.cuda.current_stream() if self.flat[bi].is_cuda else None
         if cur is not None and torch.cuda.is_current_stream_capturing():
             # Inside a HIP-graph capture the collective stays ON the capturing stream (a synchronous op: RCCL's internal

@@ -743,6 +743,52 @@ int pq3d_segment_gather(const float* table, const int64_t* index, const float* c
                         int64_t C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Instance-segmentation predictions (evaluator/instseg_eval.py:85-149 with use_dbscan = False and
+ * filter_out_no_object_queries = False: get_mask_and_scores :283-304, get_full_res_mask :272-281, the predicted boxes of
+ * record_preds :306-327) for a batch of B ragged scenes in a fixed number of launches (pq3d_amd/csrc/instseg.hip; the host
+ * side is pq3d_amd/instseg.py).  Per scene b, logits [Q, C1 = C+1], masks [S, Q] (segments first), K selections:
+ *   prob = softmax(logits)[:, :C]; the K largest of prob.flatten() (ties: lower flat index first) give query = i / C and
+ *   class = i % C; mask score = sum_v sigmoid(m) [m > 0] / (sum_v [m > 0] + 1e-6) over the scene's voxels v with
+ *   m = masks[voxel2segment[v], query] (taken over segments weighted by their voxel counts); score = prob * mask score;
+ *   full-resolution mask[p] = 2 * sum > count of [m > 0] at s1 = voxel2segment[voxel_to_full_maps[p]] over the points of
+ *   p's full-resolution segment segment_to_full_maps[p]; columns sorted by score (ties: top-k rank); boxes over the mask's
+ *   points: center = mean, extent = max - min of the raw coordinates.
+ * Concatenated index maps: scene b's voxels / points are rows [off[b], off[b+1]).  offs (device int64 [3 (B+1)]) =
+ * voff[B+1] (voxels), poff[B+1] (points), coff[B+1] (point chunks: coff[b+1] - coff[b] = ceil(P_b / PQ3D_INSTSEG_PT_CHUNK)).
+ * Every sum runs in a fixed order (no float atomics): bit-identical results run to run.
+ *
+ * pq3d_instseg_check: nvox [B*S] int32 <- voxels per segment (ids offset by b*S); stats int64[2] <- {error bits, largest
+ *   segment_to_full_maps id + 1}: bit 1 a voxel2segment id outside [0, S), bit 2 a voxel_to_full_maps id outside [0, V_b),
+ *   bit 4 a negative segment_to_full_maps id.  Both outputs are zeroed by the call.
+ * pq3d_instseg_compose (ids checked): gather[p] = b*S + voxel2segment[voff[b] + voxel_to_full_maps[p]],
+ *   key[p] = b*Sf + segment_to_full_maps[p] -- the rows / groups of the vote (pq3d_segment_plan on key with B*Sf groups,
+ *   pq3d_segment_reduce of the table with `gather`, sum mode, with count).
+ * pq3d_instseg_topk: prob [B, Q*C] fp32 scratch <- the class probabilities; then one workgroup per scene -> sel_prob /
+ *   sel_query / sel_class [B, K] in top-k order.  1 <= K <= min(PQ3D_INSTSEG_MAX_K, Q*C).
+ * pq3d_instseg_scores: table [B*S, K] fp32 0/1 <- [m > 0] in top-k order; scores [B, K] (sorted), classes [B, K] int64,
+ *   order [B, K] int32 (top-k rank of sorted column j).  ws: B * ceil(S / PQ3D_INSTSEG_SEG_CHUNK) * K * 16 bytes, 16-byte
+ *   aligned.
+ * pq3d_instseg_expand: from the vote vsum [B*Sf, K] / vcount [B*Sf] of pq3d_segment_reduce: masks [NP, K] bytes (0/1) in
+ *   sorted column order, boxes [B, K, 6] (center xyz, extent xyz; zeros where empty), box_valid [B, K] (0/1).  coords [NP, 3]
+ *   fp32.  ws: n_chunks * K * PQ3D_INSTSEG_BOX_PART_BYTES bytes, 16-byte aligned (n_chunks = coff[B]). */
+#define PQ3D_INSTSEG_MAX_K 1024
+#define PQ3D_INSTSEG_SEG_CHUNK 64
+#define PQ3D_INSTSEG_PT_CHUNK 256
+#define PQ3D_INSTSEG_BOX_PART_BYTES 64
+int pq3d_instseg_check(const int64_t* v2s, const int64_t* v2f, const int64_t* s2f, const int64_t* offs, int32_t B, int64_t S,
+                       int64_t NV, int64_t NP, int32_t* nvox, int64_t* stats, void* stream);
+int pq3d_instseg_compose(const int64_t* v2s, const int64_t* v2f, const int64_t* s2f, const int64_t* offs, int32_t B, int64_t S,
+                         int64_t Sf, int64_t NP, int64_t* gather, int64_t* key, void* stream);
+int pq3d_instseg_topk(const float* logits, int32_t B, int32_t Q, int32_t C1, int32_t K, float* prob, float* sel_prob,
+                      int32_t* sel_query, int32_t* sel_class, void* stream);
+int pq3d_instseg_scores(const float* masks, const int32_t* nvox, const float* sel_prob, const int32_t* sel_query,
+                        const int32_t* sel_class, int32_t B, int64_t S, int32_t Q, int32_t K, float* table, void* ws,
+                        int64_t ws_bytes, float* scores, int64_t* classes, int32_t* order, void* stream);
+int pq3d_instseg_expand(const float* vsum, const float* vcount, const int64_t* key, const float* coords, const int64_t* offs,
+                        const int32_t* order, int32_t B, int64_t NP, int64_t n_chunks, int32_t K, uint8_t* masks, void* ws,
+                        int64_t ws_bytes, float* boxes, uint8_t* box_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer side of the training step around the path: what Query3DTrainer.backward does after
  * loss.backward() (trainer/query3d_trainer.py:18-28): clip_grad_norm_(grad_norm) (trainer/build.py:144-145),
  * torch.optim.AdamW.step() with the parameter groups of optim/utils.py:1-18 (weight decay 0.01 except biases /

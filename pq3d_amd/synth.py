@@ -185,3 +185,66 @@ def pointcloud_inputs(M: int = 4, P: int = 300, C: int = 3, seed: int = 21) -> t
     xyz[M - 1, :, 2] *= 0.05
     rgb = r.uniform(0.0, 1.0, (M, P, C))
     return torch.from_numpy(np.concatenate([xyz, rgb], -1).astype(np.float32))
+
+
+def _cut_runs(lengths: np.ndarray, n: int) -> np.ndarray:
+    """The leading run lengths (each >= 1) that cover n items, the last one shortened to fit."""
+    end = np.cumsum(lengths)
+    k = int(np.searchsorted(end, n)) + 1
+    out = lengths[:k].astype(np.int64)
+    out[-1] -= int(end[k - 1]) - n
+    return out
+
+
+def instseg_inputs(seed: int = 5, P=(2000,), S: int = 64, Q: int = 24, C: int = 20, ninf_cols=(0, 2), mean_voxel: float = 2.0,
+                   mean_seg: float = 40.0, empty_queries: int = 2, double_class: bool = True):
+    """Seeded inputs of the instance-prediction step (InstSegEval.eval_instance_step, evaluator/instseg_eval.py:85-149) for
+    len(P) ragged scenes of P[b] points.  Returns CPU tensors: pred_logits [B, Q, C+1] (columns `ninf_cols` -inf, as the mask
+    head fills them), pred_masks [B, S, Q], and per scene voxel2segment [V_b], voxel_to_full_maps [P_b], segment_to_full_maps
+    [P_b] (int64) and raw_coordinates [P_b, 3] (fp32).
+
+    Scene layout: full-resolution segments with geometric sizes (mean `mean_seg` points) laid out along a walk; voxels are runs
+    of 1..2*mean_voxel-1 consecutive points of that walk, so some voxels straddle a segment boundary; a voxel's segment is the
+    segment of its representative (first) point, so s1 = voxel2segment[voxel_to_full_maps[p]] differs from
+    segment_to_full_maps[p] for some points, and small segments can end up without a voxel.  Points and voxels are then
+    shuffled.  The first `empty_queries` queries have all-negative mask logits and a confident class (selected, empty masks);
+    with `double_class` query Q-1 is confident in two classes (selected twice)."""
+    r = np.random.default_rng([seed, 90210])
+    B = len(P)
+    logits = r.standard_normal((B, Q, C + 1)).astype(np.float32) * 2.0
+    masks = (r.standard_normal((B, S, Q)) * 3.0).astype(np.float32)
+    v2s_l, v2f_l, s2f_l, xyz_l = [], [], [], []
+    for b in range(B):
+        n = int(P[b])
+        sizes = _cut_runs(r.geometric(1.0 / mean_seg, n), n)
+        nseg = len(sizes)
+        assert nseg <= S, f"scene {b}: {nseg} segments > S = {S}"
+        ids = r.permutation(S)[:nseg]                       # segment ids scattered over [0, S): unused ids have no voxel
+        seg_of_walk = np.repeat(ids, sizes)
+        centers = r.uniform(0.0, 8.0, (nseg, 3))
+        xyz_walk = np.repeat(centers, sizes, axis=0) + r.normal(0.0, 0.3, (n, 3))
+        vs = _cut_runs(r.integers(1, int(2 * mean_voxel), n), n)
+        nvox = len(vs)
+        vox_walk = np.repeat(np.arange(nvox), vs)
+        first = np.concatenate([[0], np.cumsum(vs)[:-1]])
+        vperm = r.permutation(nvox)                         # voxel id order shuffled
+        vnew = np.empty(nvox, np.int64)
+        vnew[vperm] = np.arange(nvox)                       # voxel vperm[i] gets id i
+        v2s = seg_of_walk[first][vperm]
+        pperm = r.permutation(n)
+        v2f = vnew[vox_walk][pperm]
+        s2f = seg_of_walk[pperm]
+        v2s_l.append(torch.from_numpy(v2s.astype(np.int64)))
+        v2f_l.append(torch.from_numpy(v2f.astype(np.int64)))
+        s2f_l.append(torch.from_numpy(s2f.astype(np.int64)))
+        xyz_l.append(torch.from_numpy(xyz_walk[pperm].astype(np.float32)))
+        for q in range(min(empty_queries, Q)):
+            masks[b, :, q] = -np.abs(masks[b, :, q]) - 0.1
+            logits[b, q, int(r.integers(0, C))] = 9.0 + q
+        if double_class and Q > empty_queries:
+            c1, c2 = r.choice([c for c in range(C) if c not in ninf_cols], 2, replace=False)
+            logits[b, Q - 1, c1], logits[b, Q - 1, c2] = 7.5, 7.0
+    for c in ninf_cols:
+        logits[:, :, c] = -np.inf
+    return dict(pred_logits=torch.from_numpy(logits), pred_masks=torch.from_numpy(masks), voxel2segment=v2s_l,
+                voxel_to_full_maps=v2f_l, segment_to_full_maps=s2f_l, raw_coordinates=xyz_l)

@@ -787,6 +787,43 @@ int pq3d_instseg_scores(const float* masks, const int32_t* nvox, const float* se
 int pq3d_instseg_expand(const float* vsum, const float* vcount, const int64_t* key, const float* coords, const int64_t* offs,
                         const int32_t* order, int32_t B, int64_t NP, int64_t n_chunks, int32_t K, uint8_t* masks, void* ws,
                         int64_t ws_bytes, float* boxes, uint8_t* box_valid, void* stream);
+/* pq3d_instseg_gt_boxes: boxes of R rows of 0/1 mask bytes (the ground-truth boxes of record_preds :326-339 from
+ *   full_masks [G', P] and raw_coordinates): rinfo (device int64 [4R + 1]) = {byte offset of row r in masks [R], its scene's
+ *   first point in coords [R], its points n_r [R], chunk offsets coff [R + 1]: coff[r+1] - coff[r] = ceil(n_r /
+ *   PQ3D_INSTSEG_GT_CHUNK)}.  boxes [R, 6] (mean center xyz, max - min extent xyz; zeros where the row is empty),
+ *   box_valid [R] (0/1).  ws: n_chunks * PQ3D_INSTSEG_BOX_PART_BYTES bytes (n_chunks = coff[R]), 16-byte aligned;
+ *   1 <= R < 65536. */
+#define PQ3D_INSTSEG_GT_CHUNK 4096
+int pq3d_instseg_gt_boxes(const uint8_t* masks, const float* coords, const int64_t* rinfo, int32_t R, int64_t n_chunks,
+                          void* ws, int64_t ws_bytes, float* boxes, uint8_t* box_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Overlap tables of instance-segmentation mask AP (assign_instances_for_scan, common/eval_instseg.py:309-367) for a batch
+ * of B ragged scenes (pq3d_amd/csrc/instseg_ap.hip; the host side is pq3d_amd/instseg_ap.py).  Inputs: masks [NP, K] 0/1
+ * bytes (scene b's points are rows [poff[b], poff[b+1])), GT ids [NP] int64 (label * PQ3D_AP_INST + instance, 0 = unlabeled)
+ * and the valid labels as a rank table lab_rank [nlab] (rank of the label among the valid ones, -1 = not valid; nlab <=
+ * PQ3D_AP_MAX_LABELS) with its inverse labels [nvalid].  A point whose id is nonzero with a valid label belongs to that id's
+ * group; every other point is void.  W = ceil(nvalid * PQ3D_AP_INST / 32) words of presence bits per scene.
+ *
+ * pq3d_ap_ids: lkey [NP] int32 (local key, -1 = void), bits [B*W], wpre [B*W] int32 (exclusive popcount prefix per word);
+ *   sizes int64 [B + 1] <- {G_b (distinct valid ids of scene b) ..., error bits: 1 = a negative id}.  Zeroes its outputs.
+ * pq3d_ap_keys: key [NP] int64 <- goff[b] + rank of the point's id in the scene, or goff[b+1] - 1 (void); goff (device
+ *   int64 [B+1]) = prefix of G_b + 1.
+ * pq3d_ap_count: out [NG, K] int32 <- per group g of the plan (pq3d_segment_plan over key with NG = goff[B] groups), the
+ *   points of g in each column.  Zeroes out.
+ * pq3d_ap_pack: per scene, at packed + toff[b] (toff device int64 [B+1]; G = G_b): gt_ids [G] (ascending), gt_verts [G],
+ *   inter [K, G], void [K], pred_verts [K] (int32).  max_entries = max over scenes of G + K*G + K. */
+#define PQ3D_AP_INST 1000
+#define PQ3D_AP_MAX_K 1024
+#define PQ3D_AP_MAX_LABELS 4096
+int pq3d_ap_ids(const int64_t* ids, const int64_t* poff, int32_t B, int64_t NP, const int32_t* lab_rank, int32_t nlab, int64_t W,
+                int32_t* lkey, uint32_t* bits, int32_t* wpre, int64_t* sizes, void* stream);
+int pq3d_ap_keys(const int32_t* lkey, const uint32_t* bits, const int32_t* wpre, const int64_t* poff, const int64_t* goff,
+                 int32_t B, int64_t NP, int64_t W, int64_t* key, void* stream);
+int pq3d_ap_count(const uint8_t* masks, int64_t K, const void* plan, int64_t N, int64_t NG, int32_t* out, void* stream);
+int pq3d_ap_pack(const int32_t* out, const void* plan, int64_t N, int64_t NG, const uint32_t* bits, const int32_t* wpre,
+                 const int32_t* labels, const int64_t* goff, const int64_t* toff, int32_t B, int64_t K, int64_t W,
+                 int64_t max_entries, int32_t* packed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer side of the training step around the path: what Query3DTrainer.backward does after

@@ -284,6 +284,12 @@ _SIGS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "pq3d_instseg_expand": [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_instseg_gt_boxes": [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_ap_ids": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5,
+    "pq3d_ap_keys": [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "pq3d_ap_count": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "pq3d_ap_pack": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int64,
+                                                                                          C.c_int64, C.c_void_p, C.c_void_p],
     "pq3d_sumsq_partials": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "pq3d_train_scalars": [C.POINTER(AdamWHp), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "pq3d_adamw": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AdamWHp), C.POINTER(OptSegments),

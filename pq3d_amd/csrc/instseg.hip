@@ -22,7 +22,9 @@
 //   (the vote sum[Sf-row, k] / count per full-resolution segment is pq3d_segment_reduce over the table, csrc/segment.hip)
 //   instseg_expand_kernel  mask[p, j] = 2 * sum[key(p), order[j]] > count[key(p)] (exact: integer-valued fp32 sums) written
 //                          as bytes in sorted column order, with per-256-point partial box sums (fp64) / minima / maxima;
-//   instseg_box_kernel     per (scene, column): the partials in chunk order -> center, extent, valid.
+//   instseg_box_kernel     per (scene, column): the partials in chunk order -> center, extent, valid;
+//   instseg_gt_part_kernel the same partials over rows of 0/1 mask bytes [G', P] (the ground-truth boxes of
+//                          record_preds :326-339), reduced by instseg_box_kernel.
 // Every sum runs in a fixed order (no float atomics): results are bit-identical run to run.
 #include "common.h"
 
@@ -429,13 +431,12 @@ __global__ __launch_bounds__(256) void instseg_expand_kernel(const float* __rest
 
 // ---- 7. boxes from the partials: one workgroup per (column, scene); thread t takes chunks t, t+256, ... then a fixed-order
 // tree over the threads (deterministic) ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void instseg_box_kernel(const BoxPart* __restrict__ part, const int64_t* __restrict__ offs, int B,
-                                                          int K, float* __restrict__ boxes, unsigned char* __restrict__ valid) {
+__global__ __launch_bounds__(256) void instseg_box_kernel(const BoxPart* __restrict__ part, const int64_t* __restrict__ coff, int K,
+                                                          float* __restrict__ boxes, unsigned char* __restrict__ valid) {
   __shared__ double rs[3][256];
   __shared__ float rmn[3][256], rmx[3][256];
   __shared__ int rn[256];
   const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int64_t* coff = offs + 2 * (B + 1);
   double s[3] = {0.0, 0.0, 0.0};
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
   int n = 0;
@@ -467,6 +468,65 @@ __global__ __launch_bounds__(256) void instseg_box_kernel(const BoxPart* __restr
     o[d] = nt > 0 ? (float)(rs[d][0] / (double)nt) : 0.f;
     o[3 + d] = nt > 0 ? rmx[d][0] - rmn[d][0] : 0.f;
     if (d == 0) valid[(long)b * K + j] = nt > 0 ? 1 : 0;
+  }
+}
+
+// ---- 8. boxes of 0/1 mask rows (the ground-truth boxes of InstSegEval.record_preds): row r = R mask bytes over the n_r points
+// of its scene; chunk c of row r (GT_CHUNK points, coff[r] + c) -> one BoxPart with the same fixed-order fp64 sums as the
+// expand kernel's, reduced by instseg_box_kernel (K = 1, one "scene" per row).  rinfo = {mask byte offset [R], first point
+// [R], points [R], chunk offsets coff [R + 1]}.
+constexpr int GT_CHUNK = PQ3D_INSTSEG_GT_CHUNK;
+__global__ __launch_bounds__(256) void instseg_gt_part_kernel(const unsigned char* __restrict__ masks, const float* __restrict__ coords,
+                                                              const int64_t* __restrict__ rinfo, int R, BoxPart* __restrict__ part) {
+  __shared__ double rs[3][256];
+  __shared__ float rmn[3][256], rmx[3][256];
+  __shared__ int rn[256];
+  const int64_t* moff = rinfo;
+  const int64_t* pfirst = rinfo + R;
+  const int64_t* npts = rinfo + 2 * R;
+  const int64_t* coff = rinfo + 3 * R;
+  const long cid = blockIdx.x;
+  const int r = scene_of(coff, R, cid);
+  const int tid = threadIdx.x;
+  const long q0 = (cid - coff[r]) * GT_CHUNK, q1 = min(q0 + GT_CHUNK, (long)npts[r]);
+  const unsigned char* m = masks + moff[r];
+  const float* xyz = coords + 3 * pfirst[r];
+  double s[3] = {0.0, 0.0, 0.0};
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  int n = 0;
+  for (long q = q0 + tid; q < q1; q += 256) {
+    if (m[q]) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const float v = xyz[3 * q + d];
+        s[d] += v; mn[d] = fminf(mn[d], v); mx[d] = fmaxf(mx[d], v);
+      }
+      ++n;
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { rs[d][tid] = s[d]; rmn[d][tid] = mn[d]; rmx[d][tid] = mx[d]; }
+  rn[tid] = n;
+  for (int h = 128; h > 0; h >>= 1) {
+    __syncthreads();
+    if (tid < h) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        rs[d][tid] += rs[d][tid + h];
+        rmn[d][tid] = fminf(rmn[d][tid], rmn[d][tid + h]);
+        rmx[d][tid] = fmaxf(rmx[d][tid], rmx[d][tid + h]);
+      }
+      rn[tid] += rn[tid + h];
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    BoxPart o;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { o.s[d] = rs[d][0]; o.mn[d] = rmn[d][0]; o.mx[d] = rmx[d][0]; }
+    o.n = rn[0];
+    o.pad[0] = o.pad[1] = o.pad[2] = 0;
+    part[cid] = o;
   }
 }
 
@@ -562,8 +622,26 @@ extern "C" int pq3d_instseg_expand(const float* vsum, const float* vcount, const
   if (n_chunks > 0)
     hipLaunchKernelGGL(instseg_expand_kernel, dim3((unsigned)n_chunks, (unsigned)((K + 63) / 64)), dim3(256), 0, s, vsum, vcount,
                        key, coords, offs, (const int*)order, (int)B, (int)K, masks, (BoxPart*)ws);
-  hipLaunchKernelGGL(instseg_box_kernel, dim3((unsigned)K, (unsigned)B), dim3(256), 0, s, (const BoxPart*)ws, offs, (int)B,
+  hipLaunchKernelGGL(instseg_box_kernel, dim3((unsigned)K, (unsigned)B), dim3(256), 0, s, (const BoxPart*)ws, offs + 2 * (B + 1),
                      (int)K, boxes, box_valid);
+  PQ_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pq3d_instseg_gt_boxes(const uint8_t* masks, const float* coords, const int64_t* rinfo, int32_t R, int64_t n_chunks,
+                                     void* ws, int64_t ws_bytes, float* boxes, uint8_t* box_valid, void* stream) {
+  PQ_DEVICE_GUARD(stream, boxes);
+  PQ_CHECK_ARG(rinfo && boxes && box_valid && R >= 1 && R < 65536 && n_chunks >= 0 &&
+               (n_chunks == 0 || (masks && coords && ws)), "pq3d_instseg_gt_boxes: bad args (1 <= R < 65536)");
+  PQ_CHECK_ARG(n_chunks < (1LL << 31), "pq3d_instseg_gt_boxes: too many points");
+  PQ_CHECK_ARG(n_chunks == 0 || (ws_bytes >= n_chunks * (int64_t)sizeof(BoxPart) && (((uintptr_t)ws) & 15) == 0),
+               "pq3d_instseg_gt_boxes: workspace smaller than n_chunks * 64 bytes or not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_chunks > 0)
+    hipLaunchKernelGGL(instseg_gt_part_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, masks, coords, rinfo, (int)R,
+                       (BoxPart*)ws);
+  hipLaunchKernelGGL(instseg_box_kernel, dim3(1u, (unsigned)R), dim3(256), 0, s, (const BoxPart*)ws, rinfo + 3 * R, 1, boxes,
+                     box_valid);
   PQ_LAUNCH_CHECK();
   return 0;
 }

@@ -248,3 +248,47 @@ def instseg_inputs(seed: int = 5, P=(2000,), S: int = 64, Q: int = 24, C: int = 
         logits[:, :, c] = -np.inf
     return dict(pred_logits=torch.from_numpy(logits), pred_masks=torch.from_numpy(masks), voxel2segment=v2s_l,
                 voxel_to_full_maps=v2f_l, segment_to_full_maps=s2f_l, raw_coordinates=xyz_l)
+
+
+def instseg_ap_scene(seed: int, P: int = 3000, K: int = 24, G: int = 12, labels=(3, 5, 7, 9, 14), invalid_labels=(1, 2),
+                     void_frac: float = 0.15, min_inst: int = 20):
+    """One synthetic scene for mask AP: per-point GT ids (label * 1000 + instance, 0 = unlabeled; a share of the void
+    points carries an invalid label), K predicted masks that mostly cover one instance (a random 60-100 % of it plus
+    scattered points; some cover two instances, some are pure noise), float32 scores and raw class ids (mostly the covered
+    instance's label, some another valid one, a few an invalid one).  Returns numpy masks [P, K] bool, ids [P] int64,
+    scores [K] float32, classes [K] int64."""
+    rng = _rng(seed, f"instseg_ap/{P}/{K}/{G}")
+    labels = np.asarray(labels, dtype=np.int64)
+    n_void = int(P * void_frac)
+    sizes = rng.dirichlet(np.full(G, 0.8)) * (P - n_void - G * min_inst)
+    sizes = (np.floor(sizes).astype(np.int64) + min_inst) if G else np.zeros(0, np.int64)
+    inst_ids = labels[rng.integers(0, len(labels), G)] * 1000 + rng.permutation(np.arange(1, 1000))[:G]
+    ids = np.zeros(P, dtype=np.int64)
+    pos = rng.permutation(P)
+    o = 0
+    for g in range(G):
+        ids[pos[o:o + sizes[g]]] = inst_ids[g]
+        o += int(sizes[g])
+    rest = pos[o:]
+    if len(invalid_labels) and len(rest):
+        bad = rest[rng.random(len(rest)) < 0.4]
+        ids[bad] = np.asarray(invalid_labels)[rng.integers(0, len(invalid_labels), len(bad))] * 1000 + rng.integers(1, 50, len(bad))
+    masks = np.zeros((P, K), dtype=bool)
+    classes = np.zeros(K, dtype=np.int64)
+    for k in range(K):
+        kind = rng.random()
+        if G and kind < 0.85:
+            tg = [rng.integers(0, G)] + ([rng.integers(0, G)] if kind > 0.75 else [])
+            for g in tg:
+                pts = np.nonzero(ids == inst_ids[g])[0]
+                masks[pts[rng.random(len(pts)) < rng.uniform(0.6, 1.0)], k] = True
+            masks[rng.integers(0, P, int(rng.integers(0, max(2, P // 50)))), k] = True
+            lab = inst_ids[tg[0]] // 1000
+            u = rng.random()
+            classes[k] = lab if u < 0.75 else (labels[rng.integers(0, len(labels))] if u < 0.93 or not len(invalid_labels)
+                                               else invalid_labels[0])
+        else:
+            masks[rng.integers(0, P, int(rng.integers(1, max(2, P // 10)))), k] = True
+            classes[k] = labels[rng.integers(0, len(labels))]
+    scores = rng.random(K).astype(np.float32)
+    return masks, ids, scores, classes

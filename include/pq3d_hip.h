@@ -798,6 +798,66 @@ int pq3d_instseg_gt_boxes(const uint8_t* masks, const float* coords, const int64
                           void* ws, int64_t ws_bytes, float* boxes, uint8_t* box_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Instance predictions with filter_out_no_object_queries and / or use_dbscan (evaluator/instseg_eval.py:104-116, 245-270;
+ * pq3d_amd/csrc/instseg.hip, pq3d_amd/csrc/instseg_dbscan.hip; host side pq3d_amd/instseg.py).  Per scene:
+ *   1. Filter: keep query q iff the argmax of its C+1 probabilities (ties: lower index, torch.argmax) is not C; query order
+ *      is kept and kept queries carry their C class probabilities (the no-object column dropped).
+ *   2. DBSCAN (min_samples = 1 only): kept query q's voxels M_q = {v : masks[voxel2segment[v], q] > 0} split into the
+ *      connected components of "((dx*dx + dy*dy) + dz*dz) <= eps*eps", evaluated in fp64 on the fp32 voxel coordinates in
+ *      exactly this order without contraction.  Each component is one column (q's class probabilities; mask = q's logits
+ *      inside the component, 0 elsewhere); columns ordered by (q, smallest voxel index of the component) -- sklearn's
+ *      label order; queries with empty M_q give no column.  The partition is unique, so the columns are deterministic.
+ *   3. Top-k over the Q'_b columns: K_b = min(K, Q'_b * C) (topk_per_scene = -1: K_b = Q'_b); flat index = column * C +
+ *      class, ties to the lower flat index.  Unlike the reference (which raises), K > Q'_b * C and scenes without columns
+ *      give short / empty records.
+ *   4. score = prob * sum_v sigmoid(m_v) [v in column] / (count + 1e-6) (with DBSCAN a voxel-level sum).
+ *   5. Full-resolution masks by the vote 2 * sum > count over segment_to_full_maps; with DBSCAN the table rows are
+ *      voxel-level (voxel_to_full_maps[p]).  Sorting and boxes as above.
+ * Grid: cells of side eps / sqrt(3) * (1 - 1e-6) per scene from its coordinate minimum; the dense cell keys of a batch are
+ * limited to PQ3D_DBSCAN_MAX_CELLS (24-bit keys).  Union-find over (query, occupied cell) nodes with atomicCAS hooks; no
+ * float atomics: bit-identical run to run.
+ *
+ * pq3d_instseg_prob: prob [B, Q*C] <- softmax(logits)[:, :C]; qvalid (nullable) [B*Q] int32 <- the filter's keep flags.
+ * pq3d_instseg_topk_ragged: per scene b the candidates prob[seg[b], seg[b+1]) (seg device int64 [B+1], multiples of C;
+ *   max_n = the largest range), rows r = flat / C with qvalid[r] == 0 (qvalid nullable) left out; kout[b] <- K_b =
+ *   kall ? kept rows : min(K, kept candidates); sel_prob / sel_query (local row) / sel_class [B, K], slots >= K_b padded
+ *   (probability 0, query 0, class 0).  1 <= K <= PQ3D_INSTSEG_MAX_K.
+ * pq3d_instseg_rank: scores / classes / order [B, K] from per-chunk partials part [B, nsc, K] double2 {sum sigmoid, count}
+ *   (the ranking step of pq3d_instseg_scores).
+ * pq3d_dbscan_bounds: bounds [B, 6] uint32 <- order-preserving codes of the per-scene minimum (bit-inverted) and maximum of
+ *   xyz [NV, 3]; stats[0] |= 8 for a non-finite coordinate (stats as zeroed by pq3d_instseg_check).
+ * pq3d_dbscan_keys: key [NV] <- dense cell key of each voxel; gtab device int64 [B, PQ3D_DBSCAN_GRID_WORDS] = {cell offset,
+ *   nx, ny, nz, fp32 bits of the grid origin x, y, z, 0} per scene.
+ * pq3d_dbscan_components: plan = pq3d_segment_plan of key over ndense cells; ncap >= occupied cells (<= NV); ws of
+ *   pq3d_dbscan_ws_bytes(NV, Q, ncap, B) bytes, 256-byte aligned; colseg device int64 [B+1] <- first column of each scene
+ *   (colseg[B] = all columns).
+ * pq3d_dbscan_columns: col [ncol, 4] int32 <- {query, head voxel, scene, 0}; colprob [ncol, C] <- the columns' probabilities.
+ * pq3d_dbscan_table: table [B * Vmax, K] fp32 0/1 of the selected columns (rows b * Vmax + local voxel) and part
+ *   [B, ceil(Vmax / PQ3D_INSTSEG_SEG_CHUNK), K] double2 (part_bytes >= that * 16). */
+#define PQ3D_DBSCAN_GRID_WORDS 8
+#define PQ3D_DBSCAN_MAX_CELLS (1 << 24)
+int pq3d_instseg_prob(const float* logits, int32_t B, int32_t Q, int32_t C1, float* prob, int32_t* qvalid, void* stream);
+int pq3d_instseg_topk_ragged(const float* prob, const int64_t* seg, const int32_t* qvalid, int32_t B, int32_t C, int32_t K,
+                             int32_t kall, int64_t max_n, float* sel_prob, int32_t* sel_query, int32_t* sel_class,
+                             int32_t* kout, void* stream);
+int pq3d_instseg_rank(const void* part, int64_t nsc, const float* sel_prob, const int32_t* sel_class, int32_t B, int32_t K,
+                      float* scores, int64_t* classes, int32_t* order, void* stream);
+int pq3d_dbscan_bounds(const float* xyz, const int64_t* voff, int32_t B, int64_t NV, uint32_t* bounds, int64_t* stats,
+                       void* stream);
+int pq3d_dbscan_keys(const float* xyz, const int64_t* voff, const int64_t* gtab, int32_t B, int64_t NV, double cell,
+                     int64_t* key, void* stream);
+int64_t pq3d_dbscan_ws_bytes(int64_t NV, int32_t Q, int64_t ncap, int32_t B);
+int pq3d_dbscan_components(const float* masks, const int64_t* v2s, const int64_t* voff, const int32_t* qvalid, const float* xyz,
+                           const int64_t* key, const int64_t* gtab, const void* plan, int64_t ndense, int32_t B, int64_t S,
+                           int32_t Q, int64_t NV, int64_t ncap, double eps, void* ws, int64_t ws_bytes, int64_t* colseg,
+                           void* stream);
+int pq3d_dbscan_columns(const float* prob, const int64_t* voff, int32_t B, int32_t Q, int32_t C, int64_t NV, int64_t ncap,
+                        int64_t ncol, const void* ws, int32_t* col, float* colprob, void* stream);
+int pq3d_dbscan_table(const float* masks, const int64_t* v2s, const int64_t* voff, const void* ws, const int32_t* col,
+                      const int64_t* colseg, const int32_t* sel, const int32_t* kout, int32_t B, int64_t S, int32_t Q, int32_t K,
+                      int64_t NV, int64_t ncap, int64_t Vmax, float* table, void* part, int64_t part_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Overlap tables of instance-segmentation mask AP (assign_instances_for_scan, common/eval_instseg.py:309-367) for a batch
  * of B ragged scenes (pq3d_amd/csrc/instseg_ap.hip; the host side is pq3d_amd/instseg_ap.py).  Inputs: masks [NP, K] 0/1
  * bytes (scene b's points are rows [poff[b], poff[b+1])), GT ids [NP] int64 (label * PQ3D_AP_INST + instance, 0 = unlabeled)

@@ -285,6 +285,18 @@ _SIGS = {
     "pq3d_instseg_expand": [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_void_p, C.c_void_p],
     "pq3d_instseg_gt_boxes": [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_instseg_prob": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_instseg_topk_ragged": [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_int64] + [C.c_void_p] * 5,
+    "pq3d_instseg_rank": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4,
+    "pq3d_dbscan_bounds": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_dbscan_keys": [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p],
+    "pq3d_dbscan_ws_bytes": [C.c_int64, C.c_int32, C.c_int64, C.c_int32],
+    "pq3d_dbscan_components": [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_double,
+                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "pq3d_dbscan_columns": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64] +
+                           [C.c_void_p] * 4,
+    "pq3d_dbscan_table": [C.c_void_p] * 8 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "pq3d_ap_ids": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5,
     "pq3d_ap_keys": [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
     "pq3d_ap_count": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
@@ -348,7 +360,7 @@ _SIGS = {
     "pq3d_allreduce_grads_wire": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "pq3d_test_wire_reduce": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
 }
-_RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes"}   # size queries: bytes (or -1), not a status code
+_RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes"}   # size queries: bytes (or -1), not a status code
 EXPORTS = sorted(list(_SIGS) + ["pq3d_last_error", "pq3d_version"])
 
 

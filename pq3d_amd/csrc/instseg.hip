@@ -12,8 +12,12 @@
 //   instseg_compose_kernel per point: the composed row voxel2segment[voxel_to_full_maps[p]] + b * S of the [B*S, K] bit
 //                          table and the batched full-resolution segment id segment_to_full_maps[p] + b * Sf;
 //   instseg_prob_kernel    softmax over the C+1 classes, one wave per query row, last column dropped -> prob [B, Q*C];
+//   instseg_filter_kernel  (filter_out_no_object_queries) per query row: 1 iff the argmax of the C+1 probabilities (ties:
+//                          lower index) is not the no-object column C;
 //   instseg_topk_kernel    one workgroup per scene: radix select of the K largest of the Q*C probabilities over their float
-//                          bits (held in registers), LDS bitonic sort by (probability desc, flat index asc);
+//                          bits (held in registers), LDS bitonic sort by (probability desc, flat index asc); the RAGGED form
+//                          selects K_b = min(K, candidates) of scene b's own candidate range (per-scene offsets) and leaves
+//                          out the rows of filtered queries (stored as bit pattern 0, below every kept candidate's bits + 1);
 //   instseg_table_kernel   the [B*S, K] fp32 0/1 table [m > 0] (m = pred_masks[b][s][query_k]) and per-64-segment partial
 //                          sums of n_s * sigmoid(m) * [m > 0] and n_s * [m > 0] (n_s = voxels of segment s): the voxel sums
 //                          of the reference taken over segments; no [V, K] matrix;
@@ -182,29 +186,81 @@ __global__ __launch_bounds__(256) void instseg_prob_kernel(const float* __restri
   for (int c = lane; c < C; c += 64) out[c] = expf(row[c] - m) / s;
 }
 
+// 3a'. valid[b*Q + q] = argmax_c softmax(logits[b, q, :])[c] != C over the C+1 probabilities (ties: lower index, as
+// torch.argmax), with the same expression as instseg_prob_kernel (grid (ceil(Q / 4), B), one wave per query row)
+__global__ __launch_bounds__(256) void instseg_filter_kernel(const float* __restrict__ logits, int Q, int C1,
+                                                             int* __restrict__ valid) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y, lane = threadIdx.x & 63;
+  if (q >= Q) return;
+  const float* row = logits + ((long)b * Q + q) * C1;
+  float m = -INFINITY;
+  for (int c = lane; c < C1; c += 64) m = fmaxf(m, row[c]);
+  m = wave_max(m);
+  float s = 0.f;
+  for (int c = lane; c < C1; c += 64) s += expf(row[c] - m);
+  s = wave_sum(s);
+  float best = -INFINITY;
+  int bi = C1;
+  for (int c = lane; c < C1; c += 64) {
+    const float p = expf(row[c] - m) / s;
+    if (p > best || bi == C1) { best = p; bi = c; }       // ascending c per lane: strict > keeps the lower index
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const float ob = __shfl_xor(best, d);
+    const int oi = __shfl_xor(bi, d);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  if (lane == 0) valid[(long)b * Q + q] = bi != C1 - 1 ? 1 : 0;
+}
+
 // sort key of a candidate: ascending key = descending probability, then ascending flat index (probabilities are >= 0, so
 // their bit patterns order like the values)
 PQ_DEV unsigned long long cand_key(unsigned u, int i) { return ((unsigned long long)(~u) << 32) | (unsigned)i; }
 
 // 3b. one workgroup per scene over the n = Q*C probability bits: candidate i = tid + 1024 r lives in register r of thread tid
 // (R > 0: n <= 1024 R, every pass runs on chip) or is re-read from the L2-resident prob array (R = 0, any n).
-template <int R>
+// RAGGED: scene b's candidates are prob[seg[b], seg[b+1]) (seg[b] a multiple of C, n = the largest range); a candidate of
+// row r = (seg[b] + i) / C with qvalid[r] == 0 is left out.  Candidates are held as bits + 1 (0 = left out: below every
+// kept one, so never selected while K_b <= kept); K_b = kall ? kept rows : min(K, kept candidates) (<= K), written to
+// kout[b]; slots [K_b, K) of the outputs are padding (probability 0, query 0, class 0).
+template <int R, bool RAGGED>
 __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restrict__ prob, int n, int C, int K,
                                                             float* __restrict__ sel_prob, int* __restrict__ sel_query,
-                                                            int* __restrict__ sel_class) {
+                                                            int* __restrict__ sel_class, const int64_t* __restrict__ seg,
+                                                            const int* __restrict__ qvalid, int kall, int* __restrict__ kout) {
   __shared__ unsigned long long keys[MAX_K];
   __shared__ int hist[256];
   __shared__ int sm[17];
   __shared__ int pick[2];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const unsigned* U = (const unsigned*)prob + (long)b * n;
+  const long base0 = RAGGED ? (long)seg[b] : (long)b * n;
+  if constexpr (RAGGED) n = (int)(seg[b + 1] - seg[b]);
+  const unsigned* U = (const unsigned*)prob + base0;
+  int Kb = K;
+  if constexpr (RAGGED) {
+    const int rows = n / C;
+    int kept = 0;
+    for (int r0 = 0; r0 < rows; r0 += 1024) {
+      const int r = r0 + tid;
+      int tot;
+      (void)block_excl_scan_i(r < rows && (!qvalid || qvalid[base0 / C + r]) ? 1 : 0, sm, &tot);
+      kept += tot;
+    }
+    const long kc = (long)kept * C;
+    Kb = kall ? kept : (int)(kc < (long)K ? kc : (long)K);
+    if (Kb > K) Kb = K;
+    if (tid == 0) kout[b] = Kb;
+  }
+  // bits of candidate i (RAGGED: + 1, 0 when out of range or left out)
+  auto load = [&](int i) -> unsigned {
+    if constexpr (RAGGED) return i < n && (!qvalid || qvalid[base0 / C + i / C]) ? U[i] + 1u : 0u;
+    else return i < n ? U[i] : 0u;
+  };
   unsigned reg[R > 0 ? R : 1];
   if constexpr (R > 0) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int i = tid + 1024 * r;
-      reg[r] = i < n ? U[i] : 0u;
-    }
+    for (int r = 0; r < R; ++r) reg[r] = load(tid + 1024 * r);
   }
   // f(i, u) for every candidate slot of this thread, in ascending tile order (the same trip count in every thread)
   auto for_each = [&](auto&& f) {
@@ -214,13 +270,13 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
     } else {
       for (int base = 0; base < n; base += 1024) {
         const int i = base + tid;
-        f(i, i < n ? U[i] : 0u);
+        f(i, load(i));
       }
     }
   };
   // radix select of the K-th largest bit pattern, 8 bits per pass from the top
   unsigned prefix = 0, pmask = 0;
-  int need = K;
+  int need = Kb;
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
     if (tid < 256) hist[tid] = 0;
@@ -246,7 +302,7 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
   }
   // the K survivors: every candidate above the threshold, and the `need` lowest flat indices equal to it
   const unsigned T = prefix;
-  const int n_gt = K - need;
+  const int n_gt = Kb - need;
   int gt_carry = 0, eq_carry = 0;
   for_each([&](int i, unsigned u) {
     const int gt = i < n && u > T, eq = i < n && u == T;
@@ -263,16 +319,20 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
     gt_carry += tot & 0xffff;
     eq_carry += tot >> 16;
   });
-  const int Kp = pow2_ceil(K);
-  if (tid >= K && tid < Kp) keys[tid] = ~0ull;
+  const int Kp = pow2_ceil(Kb);
+  if (tid >= Kb && tid < Kp) keys[tid] = ~0ull;
   bitonic_sort_u64(keys, Kp);
-  if (tid < K) {
+  if (tid < Kb) {
     const unsigned long long k = keys[tid];
     const int i = (int)(k & 0xffffffffu);
     const int q = i / C;
-    sel_prob[(long)b * K + tid] = __uint_as_float(~(unsigned)(k >> 32));
+    sel_prob[(long)b * K + tid] = __uint_as_float(~(unsigned)(k >> 32) - (RAGGED ? 1u : 0u));
     sel_query[(long)b * K + tid] = q;
     sel_class[(long)b * K + tid] = i - q * C;
+  } else if (RAGGED && tid < K) {
+    sel_prob[(long)b * K + tid] = 0.f;
+    sel_query[(long)b * K + tid] = 0;
+    sel_class[(long)b * K + tid] = 0;
   }
 }
 constexpr int TOPK_REGS = 48;    // register-resident candidates up to n = 49 152 (Q = 200 x C = 200 = 40 000)
@@ -581,11 +641,55 @@ extern "C" int pq3d_instseg_topk(const float* logits, int32_t B, int32_t Q, int3
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(instseg_prob_kernel, dim3((unsigned)((Q + 3) / 4), (unsigned)B), dim3(256), 0, s, logits, (int)Q, (int)C1, prob);
   if (n <= 1024L * TOPK_REGS)
-    hipLaunchKernelGGL(instseg_topk_kernel<TOPK_REGS>, dim3((unsigned)B), dim3(1024), 0, s, (const float*)prob, (int)n,
-                       (int)(C1 - 1), (int)K, sel_prob, (int*)sel_query, (int*)sel_class);
+    hipLaunchKernelGGL((instseg_topk_kernel<TOPK_REGS, false>), dim3((unsigned)B), dim3(1024), 0, s, (const float*)prob, (int)n,
+                       (int)(C1 - 1), (int)K, sel_prob, (int*)sel_query, (int*)sel_class, (const int64_t*)nullptr,
+                       (const int*)nullptr, 0, (int*)nullptr);
   else
-    hipLaunchKernelGGL(instseg_topk_kernel<0>, dim3((unsigned)B), dim3(1024), 0, s, (const float*)prob, (int)n, (int)(C1 - 1),
-                       (int)K, sel_prob, (int*)sel_query, (int*)sel_class);
+    hipLaunchKernelGGL((instseg_topk_kernel<0, false>), dim3((unsigned)B), dim3(1024), 0, s, (const float*)prob, (int)n,
+                       (int)(C1 - 1), (int)K, sel_prob, (int*)sel_query, (int*)sel_class, (const int64_t*)nullptr,
+                       (const int*)nullptr, 0, (int*)nullptr);
+  PQ_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pq3d_instseg_prob(const float* logits, int32_t B, int32_t Q, int32_t C1, float* prob, int32_t* qvalid,
+                                 void* stream) {
+  PQ_DEVICE_GUARD(stream, logits);
+  PQ_CHECK_ARG(logits && prob && B >= 1 && Q >= 1 && C1 >= 2 && B < 65536, "pq3d_instseg_prob: bad args (B < 65536, Q >= 1, C1 >= 2)");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(instseg_prob_kernel, dim3((unsigned)((Q + 3) / 4), (unsigned)B), dim3(256), 0, s, logits, (int)Q, (int)C1, prob);
+  if (qvalid)
+    hipLaunchKernelGGL(instseg_filter_kernel, dim3((unsigned)((Q + 3) / 4), (unsigned)B), dim3(256), 0, s, logits, (int)Q,
+                       (int)C1, (int*)qvalid);
+  PQ_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pq3d_instseg_topk_ragged(const float* prob, const int64_t* seg, const int32_t* qvalid, int32_t B, int32_t C,
+                                        int32_t K, int32_t kall, int64_t max_n, float* sel_prob, int32_t* sel_query,
+                                        int32_t* sel_class, int32_t* kout, void* stream) {
+  PQ_DEVICE_GUARD(stream, seg);
+  PQ_CHECK_ARG(prob && seg && sel_prob && sel_query && sel_class && kout && B >= 1 && B < 65536 && C >= 1 && K >= 1 &&
+               K <= MAX_K && max_n >= 0, "pq3d_instseg_topk_ragged: bad args (B < 65536, C >= 1, 1 <= K <= 1024)");
+  PQ_CHECK_ARG(max_n < (1LL << 31) - 1024, "pq3d_instseg_topk_ragged: candidates per scene must fit 31 bits");
+  hipStream_t s = (hipStream_t)stream;
+  if (max_n <= 1024L * TOPK_REGS)
+    hipLaunchKernelGGL((instseg_topk_kernel<TOPK_REGS, true>), dim3((unsigned)B), dim3(1024), 0, s, prob, 0, (int)C, (int)K,
+                       sel_prob, (int*)sel_query, (int*)sel_class, seg, (const int*)qvalid, (int)kall, (int*)kout);
+  else
+    hipLaunchKernelGGL((instseg_topk_kernel<0, true>), dim3((unsigned)B), dim3(1024), 0, s, prob, 0, (int)C, (int)K, sel_prob,
+                       (int*)sel_query, (int*)sel_class, seg, (const int*)qvalid, (int)kall, (int*)kout);
+  PQ_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pq3d_instseg_rank(const void* part, int64_t nsc, const float* sel_prob, const int32_t* sel_class, int32_t B,
+                                 int32_t K, float* scores, int64_t* classes, int32_t* order, void* stream) {
+  PQ_DEVICE_GUARD(stream, sel_prob);
+  PQ_CHECK_ARG(part && sel_prob && sel_class && scores && classes && order && B >= 1 && B < 65536 && K >= 1 && K <= MAX_K &&
+               nsc >= 0 && nsc < (1LL << 31), "pq3d_instseg_rank: bad args");
+  hipLaunchKernelGGL(instseg_rank_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream, (const double2*)part, (int)nsc,
+                     sel_prob, (const int*)sel_class, (int)K, scores, classes, (int*)order);
   PQ_LAUNCH_CHECK();
   return 0;
 }

@@ -16,11 +16,31 @@ Semantics (use_dbscan = False, filter_out_no_object_queries = False), per scene 
   6. Boxes over the points of each mask: center = mean, extent = max - min of raw_coordinates; box_valid = mask not empty
      (the reference leaves such boxes out of bbox_preds but keeps the mask in preds).
 Classes are the C-class ids, before any dataset label mapping.  Results are bit-identical run to run.
+
+filter_out_no_object_queries / use_dbscan (instseg_eval.py:104-116, 245-270; csrc/instseg_dbscan.hip), per scene:
+  F. Filter: keep the queries whose argmax over the C+1 probabilities (ties: lower index, as torch.argmax) is not C, in
+     query order, with their C class probabilities (the no-object column dropped).  The reference compares with the literal
+     200, which is "not C" for the shipped C = 200.
+  D. DBSCAN (min_samples = 1 only, so every point is a core point): kept query q's voxels M_q = {v : m(v, q) > 0} split into
+     the connected components of "((dx*dx + dy*dy) + dz*dz) <= eps*eps", evaluated in fp64 on the fp32 voxel coordinates in
+     exactly this order without contraction.  Each component is one column with q's class probabilities; its mask is q's
+     logits inside the component and 0 elsewhere.  Columns are ordered by q, then by the component's smallest voxel index
+     (sklearn's label order); a query with an empty M_q gives no column.  The partition is unique, so the columns are
+     deterministic whatever order the kernels join them in.
+  Top-k then runs over the Q'_b columns: K_b = min(K, Q'_b * C) (topk_per_scene = -1: K_b = Q'_b), flat index = column * C
+  + class, ties to the lower flat index.  The reference raises on K > Q'_b * C and on a scene without columns; here those
+  give a short record or an empty one (masks [P_b, 0]), so K_b may differ from scene to scene.  With DBSCAN the mask score
+  is a voxel-level sum (a component can cut a segment in two) and the vote rows are voxel-level: voxel_to_full_maps[p]
+  instead of voxel2segment[voxel_to_full_maps[p]].  The cell grid of a DBSCAN call (cells of side eps / sqrt(3) per scene)
+  is limited to 2^24 cells over the batch.  A DBSCAN call makes two device-to-host reads (index checks + coordinate bounds,
+  then the column counts); the filter alone keeps the one read.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+import math
+from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -31,9 +51,12 @@ SEG_CHUNK = 64           # PQ3D_INSTSEG_SEG_CHUNK
 PT_CHUNK = 256           # PQ3D_INSTSEG_PT_CHUNK
 MAX_K = 1024             # PQ3D_INSTSEG_MAX_K
 BOX_PART_BYTES = 64      # PQ3D_INSTSEG_BOX_PART_BYTES
+GRID_WORDS = 8           # PQ3D_DBSCAN_GRID_WORDS
+MAX_CELLS = 1 << 24      # PQ3D_DBSCAN_MAX_CELLS: cells of a DBSCAN call's grid over the batch (24-bit cell keys)
 _ERRORS = {1: "voxel2segment holds ids outside [0, S)",
            2: "voxel_to_full_maps holds ids outside [0, number of voxels of the scene)",
-           4: "segment_to_full_maps holds negative ids"}
+           4: "segment_to_full_maps holds negative ids",
+           8: "voxel_coordinates holds non-finite values"}
 
 
 def _cat(ts: Sequence[torch.Tensor], dtype, what: str, dev) -> torch.Tensor:
@@ -45,7 +68,10 @@ def _cat(ts: Sequence[torch.Tensor], dtype, what: str, dev) -> torch.Tensor:
 
 def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, voxel2segment: Sequence[torch.Tensor],
                          voxel_to_full_maps: Sequence[torch.Tensor], segment_to_full_maps: Sequence[torch.Tensor],
-                         raw_coordinates: Sequence[torch.Tensor], topk_per_scene: int = 100) -> List[Dict[str, torch.Tensor]]:
+                         raw_coordinates: Sequence[torch.Tensor], topk_per_scene: int = 100,
+                         filter_out_no_object_queries: bool = False, use_dbscan: bool = False,
+                         voxel_coordinates: Optional[Sequence[torch.Tensor]] = None,
+                         dbscan_eps: float = 0.95) -> List[Dict[str, torch.Tensor]]:
     """Per-scene instance predictions of ``pred_logits`` [B, Q, C+1] (predictions_class[-1]) and ``pred_masks`` [B, S, Q]
     (predictions_mask[-1]), both fp32 on the device.  The index maps and coordinates are per-scene lists of device tensors:
     ``voxel2segment[b]`` [V_b] int64 (segment of each voxel), ``voxel_to_full_maps[b]`` [P_b] int64 (voxel of each point),
@@ -53,7 +79,12 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
 
     Returns one dict per scene: ``masks`` [P_b, K] bool (views into one buffer), ``scores`` [K] fp32, ``classes`` [K] int64,
     ``boxes`` [K, 6] fp32 (center xyz, extent xyz; zeros where the mask is empty) and ``box_valid`` [K] bool, all sorted by
-    score.  Index values outside their tables raise ValueError."""
+    score.  Index values outside their tables raise ValueError.
+
+    ``filter_out_no_object_queries`` / ``use_dbscan``: the reference's eval options (module docstring); ``voxel_coordinates``
+    (required with ``use_dbscan``) is a per-scene list of [V_b, 3] fp32 device tensors in voxel2segment[b] order (the
+    reference's voxel_features[:, -3:] split by scene), ``dbscan_eps`` the neighbourhood radius (the reference hard-codes
+    0.95).  With either option the record length K_b may differ from scene to scene."""
     if pred_logits.dim() != 3 or pred_masks.dim() != 3:
         raise ValueError("pred_logits must be [B, Q, C+1] and pred_masks [B, S, Q]")
     assert pred_logits.dtype == torch.float32 and pred_masks.dtype == torch.float32, \
@@ -70,15 +101,28 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     if B < 1 or S < 1 or C1 < 2:
         raise ValueError("need B >= 1, S >= 1 and C+1 >= 2")
     C_ = C1 - 1
-    K = Q if int(topk_per_scene) == -1 else int(topk_per_scene)
-    if not 1 <= K <= min(MAX_K, Q * C_):
+    kall = int(topk_per_scene) == -1
+    K = Q if kall else int(topk_per_scene)
+    ragged = bool(filter_out_no_object_queries) or bool(use_dbscan)
+    if not ragged and not 1 <= K <= min(MAX_K, Q * C_):
         raise ValueError(f"topk_per_scene must be -1 or in [1, min({MAX_K}, Q*C = {Q * C_})], got {topk_per_scene}")
+    if ragged and not (1 <= K <= MAX_K or (kall and use_dbscan)):
+        raise ValueError(f"topk_per_scene must be -1 or in [1, {MAX_K}], got {topk_per_scene}")
+    if use_dbscan:
+        eps = float(dbscan_eps)
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"dbscan_eps must be a finite number > 0, got {dbscan_eps}")
+        if voxel_coordinates is None or len(voxel_coordinates) != B:
+            raise ValueError("use_dbscan needs voxel_coordinates: one [V_b, 3] fp32 device tensor per scene")
     V = [int(t.numel()) for t in voxel2segment]
     P = [int(t.numel()) for t in voxel_to_full_maps]
     for b in range(B):
         if int(segment_to_full_maps[b].numel()) != P[b] or tuple(raw_coordinates[b].shape) != (P[b], 3):
             raise ValueError(f"scene {b}: segment_to_full_maps [P] and raw_coordinates [P, 3] must match "
                              f"voxel_to_full_maps (P = {P[b]})")
+        if use_dbscan and tuple(voxel_coordinates[b].shape) != (V[b], 3):
+            raise ValueError(f"scene {b}: voxel_coordinates must be [V, 3] with V = {V[b]} (voxel2segment), "
+                             f"got {tuple(voxel_coordinates[b].shape)}")
     v2s = _cat(voxel2segment, torch.int64, "voxel2segment", dev)
     v2f = _cat(voxel_to_full_maps, torch.int64, "voxel_to_full_maps", dev)
     s2f = _cat(segment_to_full_maps, torch.int64, "segment_to_full_maps", dev)
@@ -106,13 +150,26 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     L.check(timed("pq3d_instseg_check", f"B{B}V{NV}P{NP}", 0.0, NV * 8.0 + NP * 16.0 + B * S * 4.0,
                   lib.pq3d_instseg_check, L.ptr(v2s), L.ptr(v2f), L.ptr(s2f), L.ptr(offs), B, S, NV, NP, L.ptr(nvox),
                   L.ptr(stats), st), "pq3d_instseg_check")
+    if use_dbscan:
+        xyzv = _cat(voxel_coordinates, torch.float32, "voxel_coordinates", dev)
+        return _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h, stats, B, S, Q, C1, K, kall,
+                                   bool(filter_out_no_object_queries), eps, V, P, n_chunks)
     # 2. softmax + top-K
     prob = torch.empty(B, Q * C_, dtype=torch.float32, device=dev)
     sel_prob = torch.empty(B, K, dtype=torch.float32, device=dev)
     sel_query, sel_class = torch.empty(B, K, **i32), torch.empty(B, K, **i32)
-    L.check(timed("pq3d_instseg_topk", f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C1 * 4.0 + B * K * 12.0,
-                  lib.pq3d_instseg_topk, L.ptr(logits), B, Q, C1, K, L.ptr(prob), L.ptr(sel_prob), L.ptr(sel_query),
-                  L.ptr(sel_class), st), "pq3d_instseg_topk")
+    if ragged:      # the filter alone: dropped queries' candidates left out of the select (query order kept: no compaction)
+        qvalid, kout = torch.empty(B * Q, **i32), torch.empty(B, **i32)
+        seg = torch.arange(0, (B + 1) * Q * C_, Q * C_, dtype=torch.int64).to(dev)
+        L.check(timed("pq3d_instseg_prob", f"B{B}Q{Q}C{C1}f", 0.0, B * Q * C1 * 8.0, lib.pq3d_instseg_prob, L.ptr(logits), B,
+                      Q, C1, L.ptr(prob), L.ptr(qvalid), st), "pq3d_instseg_prob")
+        L.check(timed("pq3d_instseg_topk_ragged", f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C_ * 4.0 + B * K * 12.0,
+                      lib.pq3d_instseg_topk_ragged, L.ptr(prob), L.ptr(seg), L.ptr(qvalid), B, C_, K, int(kall), Q * C_,
+                      L.ptr(sel_prob), L.ptr(sel_query), L.ptr(sel_class), L.ptr(kout), st), "pq3d_instseg_topk_ragged")
+    else:
+        L.check(timed("pq3d_instseg_topk", f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C1 * 4.0 + B * K * 12.0,
+                      lib.pq3d_instseg_topk, L.ptr(logits), B, Q, C1, K, L.ptr(prob), L.ptr(sel_prob), L.ptr(sel_query),
+                      L.ptr(sel_class), st), "pq3d_instseg_topk")
     # 3. bit table [B*S, K] (top-k order) + mask scores, sorted by score
     nsc = (S + SEG_CHUNK - 1) // SEG_CHUNK
     table = torch.empty(B * S, K, dtype=torch.float32, device=dev)
@@ -125,13 +182,32 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
                   L.ptr(sel_class), B, S, Q, K, L.ptr(table), L.ptr(ws), ws.numel(), L.ptr(scores), L.ptr(classes),
                   L.ptr(order), st), "pq3d_instseg_scores")
 
-    err, sf = (int(x) for x in stats.cpu().tolist())        # the one device-to-host read of the call
+    if ragged:
+        host = torch.cat((stats, kout.to(torch.int64))).cpu().tolist()     # the one device-to-host read of the call
+        err, sf, Kb = int(host[0]), int(host[1]), [int(x) for x in host[2:]]
+    else:
+        err, sf = (int(x) for x in stats.cpu().tolist())        # the one device-to-host read of the call
+        Kb = [K] * B
+    Sf = _check_stats(err, sf, B)
+
+    return _vote_and_boxes(v2s, v2f, s2f, xyz, offs, offs_h, table, order, scores, classes, B, S, Sf, K, Kb, P, n_chunks)
+
+
+def _check_stats(err: int, sf: int, B: int) -> int:
     if err:
         raise ValueError("instance_predictions: " + "; ".join(m for bit, m in _ERRORS.items() if err & bit))
     Sf = max(sf, 1)
     if B * Sf >= (1 << 31) - 65536:
         raise ValueError(f"segment_to_full_maps ids too large for a batched grouping (B * (max id + 1) = {B * Sf})")
+    return Sf
 
+
+def _vote_and_boxes(v2s, v2f, s2f, xyz, offs, offs_h, table, order, scores, classes, B, S, Sf, K, Kb, P, n_chunks):
+    """Steps 4-5 on the 0/1 table [B*S, K] whose row of point p is b*S + v2s[voff[b] + voxel_to_full_maps[p]]; scene b's
+    record keeps its first Kb[b] sorted columns."""
+    dev = table.device
+    lib, st = L.lib(), L.stream()
+    NP = sum(P)
     # 4. vote per full-resolution segment: rows voxel2segment[voxel_to_full_maps[p]] of the table, grouped by segment_to_full_maps
     gather = torch.empty(NP, dtype=torch.int64, device=dev)
     key = torch.empty(NP, dtype=torch.int64, device=dev)
@@ -154,6 +230,112 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     res = []
     p0 = offs_h[B + 1]
     for b in range(B):
-        res.append(dict(masks=out[p0:p0 + P[b]], scores=scores[b], classes=classes[b], boxes=boxes[b], box_valid=valid[b]))
+        k = Kb[b]
+        if k == K:
+            res.append(dict(masks=out[p0:p0 + P[b]], scores=scores[b], classes=classes[b], boxes=boxes[b], box_valid=valid[b]))
+        else:
+            res.append(dict(masks=out[p0:p0 + P[b], :k], scores=scores[b, :k], classes=classes[b, :k], boxes=boxes[b, :k],
+                            box_valid=valid[b, :k]))
         p0 += P[b]
     return res
+
+
+def _empty_records(P, dev):
+    return [dict(masks=torch.zeros(p, 0, dtype=torch.bool, device=dev), scores=torch.zeros(0, dtype=torch.float32, device=dev),
+                 classes=torch.zeros(0, dtype=torch.int64, device=dev), boxes=torch.zeros(0, 6, dtype=torch.float32, device=dev),
+                 box_valid=torch.zeros(0, dtype=torch.bool, device=dev)) for p in P]
+
+
+def _fdec(code: int) -> float:
+    """Inverse of the kernels' order-preserving float code."""
+    u = (code & 0x7FFFFFFF) if code & 0x80000000 else (~code & 0xFFFFFFFF)
+    return float(np.array([u], dtype=np.uint32).view(np.float32)[0])
+
+
+def _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h, stats, B, S, Q, C1, K, kall, filt, eps, V, P,
+                        n_chunks):
+    dev = logits.device
+    lib, st = L.lib(), L.stream()
+    i32 = dict(dtype=torch.int32, device=dev)
+    C_ = C1 - 1
+    NV = sum(V)
+    # D1. coordinate bounds + non-finite flag, class probabilities (+ filter flags); read 1: flags, Sf, bounds
+    bounds = torch.empty(B * 6, **i32)
+    L.check(timed("pq3d_dbscan_bounds", f"B{B}V{NV}", 0.0, NV * 12.0, lib.pq3d_dbscan_bounds, L.ptr(xyzv), L.ptr(offs), B, NV,
+                  L.ptr(bounds), L.ptr(stats), st), "pq3d_dbscan_bounds")
+    prob = torch.empty(B, Q * C_, dtype=torch.float32, device=dev)
+    qvalid = torch.empty(B * Q, **i32) if filt else None
+    L.check(timed("pq3d_instseg_prob", f"B{B}Q{Q}C{C1}{'f' if filt else ''}", 0.0, B * Q * C1 * 8.0, lib.pq3d_instseg_prob,
+                  L.ptr(logits), B, Q, C1, L.ptr(prob), L.ptr(qvalid), st), "pq3d_instseg_prob")
+    host = torch.cat((stats, bounds.to(torch.int64) & 0xFFFFFFFF)).cpu().tolist()
+    Sf = _check_stats(int(host[0]), int(host[1]), B)
+    if NV == 0:
+        return _empty_records(P, dev)
+    # D2. grid per scene: cells of side eps / sqrt(3) * (1 - 1e-6) from the scene's minimum
+    cell = eps / math.sqrt(3.0) * (1.0 - 1e-6)
+    gtab, ndense = [], 0
+    for b in range(B):
+        if V[b] == 0:
+            lo, n = [0.0] * 3, [1, 1, 1]
+        else:
+            code = [int(x) for x in host[2 + 6 * b:8 + 6 * b]]
+            lo = [_fdec(~c & 0xFFFFFFFF) for c in code[:3]]
+            hi = [_fdec(c) for c in code[3:]]
+            n = [int(math.floor((hi[d] - lo[d]) / cell)) + 1 for d in range(3)]
+        cells = n[0] * n[1] * n[2]
+        if ndense + cells > MAX_CELLS:
+            raise ValueError(f"use_dbscan: the cell grid (side {cell:.4g}) of the batch needs more than 2^24 cells "
+                             f"(scene {b}: {n[0]} x {n[1]} x {n[2]}); use a larger dbscan_eps or fewer scenes per call")
+        gtab.append([ndense, n[0], n[1], n[2]] + [int(np.array([x], np.float32).view(np.uint32)[0]) for x in lo] + [0])
+        ndense += cells
+    gtab = torch.tensor(gtab, dtype=torch.int64).reshape(-1).to(dev)
+    key = torch.empty(NV, dtype=torch.int64, device=dev)
+    L.check(timed("pq3d_dbscan_keys", f"B{B}V{NV}", 0.0, NV * 20.0, lib.pq3d_dbscan_keys, L.ptr(xyzv), L.ptr(offs), L.ptr(gtab),
+                  B, NV, cell, L.ptr(key), st), "pq3d_dbscan_keys")
+    plan = SegmentPlan(key, ndense)
+    ncap = min(NV, ndense)
+    if Q * ncap >= (1 << 31) - 1 or Q * (NV // 64 + 1) >= (1 << 31):
+        raise ValueError(f"use_dbscan: Q * cells ({Q} * {ncap}) must fit 31 bits")
+    wsb = int(lib.pq3d_dbscan_ws_bytes(NV, Q, ncap, B))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    colseg = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    L.check(timed("pq3d_dbscan_components", f"B{B}V{NV}Q{Q}", 0.0, NV * (Q * 4.0 + 40.0), lib.pq3d_dbscan_components,
+                  L.ptr(masks_in), L.ptr(v2s), L.ptr(offs), L.ptr(qvalid), L.ptr(xyzv), L.ptr(key), L.ptr(gtab), L.ptr(plan.buf),
+                  ndense, B, S, Q, NV, ncap, eps, L.ptr(ws), wsb, L.ptr(colseg), st), "pq3d_dbscan_components")
+    cs = [int(x) for x in colseg.cpu().tolist()]                   # read 2: the columns per scene
+    Qp = [cs[b + 1] - cs[b] for b in range(B)]
+    Kb = [q if kall else min(K, q * C_) for q in Qp]
+    Kmax, ncol = max(Kb), cs[B]
+    if kall and Kmax > MAX_K:
+        raise ValueError(f"topk_per_scene = -1 selects one entry per column: {Kmax} columns > {MAX_K}")
+    if Kmax == 0:
+        return _empty_records(P, dev)
+    # D3. columns in (query, smallest voxel) order, their probabilities, top-K over each scene's Q'_b * C candidates
+    col = torch.empty(ncol * 4, **i32)
+    colprob = torch.empty(ncol * C_, dtype=torch.float32, device=dev)
+    L.check(timed("pq3d_dbscan_columns", f"B{B}N{ncol}C{C_}", 0.0, ncol * C_ * 8.0, lib.pq3d_dbscan_columns, L.ptr(prob),
+                  L.ptr(offs), B, Q, C_, NV, ncap, ncol, L.ptr(ws), L.ptr(col), L.ptr(colprob), st), "pq3d_dbscan_columns")
+    seg = colseg * C_
+    sel_prob = torch.empty(B, Kmax, dtype=torch.float32, device=dev)
+    sel_query, sel_class, kout = torch.empty(B, Kmax, **i32), torch.empty(B, Kmax, **i32), torch.empty(B, **i32)
+    L.check(timed("pq3d_instseg_topk_ragged", f"B{B}N{ncol}C{C_}K{Kmax}", 0.0, ncol * C_ * 4.0 + B * Kmax * 12.0,
+                  lib.pq3d_instseg_topk_ragged, L.ptr(colprob), L.ptr(seg), None, B, C_, Kmax, int(kall), max(Qp) * C_,
+                  L.ptr(sel_prob), L.ptr(sel_query), L.ptr(sel_class), L.ptr(kout), st), "pq3d_instseg_topk_ragged")
+    # D4. voxel-level table [B * Vmax, K] + scores, ranked
+    Vmax = max(V)
+    nch = (Vmax + SEG_CHUNK - 1) // SEG_CHUNK
+    table = torch.empty(B * Vmax, Kmax, dtype=torch.float32, device=dev)
+    part = torch.empty(B * nch * Kmax * 16, dtype=torch.uint8, device=dev)
+    L.check(timed("pq3d_dbscan_table", f"B{B}V{NV}K{Kmax}", 0.0, NV * (Kmax * 12.0 + 8.0), lib.pq3d_dbscan_table,
+                  L.ptr(masks_in), L.ptr(v2s), L.ptr(offs), L.ptr(ws), L.ptr(col), L.ptr(colseg), L.ptr(sel_query), L.ptr(kout),
+                  B, S, Q, Kmax, NV, ncap, Vmax, L.ptr(table), L.ptr(part), part.numel(), st), "pq3d_dbscan_table")
+    scores = torch.empty(B, Kmax, dtype=torch.float32, device=dev)
+    classes = torch.empty(B, Kmax, dtype=torch.int64, device=dev)
+    order = torch.empty(B, Kmax, **i32)
+    L.check(timed("pq3d_instseg_rank", f"B{B}K{Kmax}", 0.0, B * nch * Kmax * 16.0, lib.pq3d_instseg_rank, L.ptr(part), nch,
+                  L.ptr(sel_prob), L.ptr(sel_class), B, Kmax, L.ptr(scores), L.ptr(classes), L.ptr(order), st),
+            "pq3d_instseg_rank")
+    # D5. vote on voxel-level rows: the table row of point p is b * Vmax + voxel_to_full_maps[p]
+    local = torch.cat([torch.arange(v, dtype=torch.int64, device=dev) for v in V])
+    return _vote_and_boxes(local, v2f, s2f, xyz, offs, offs_h, table, order, scores, classes, B, Vmax, Sf, Kmax, Kb, P,
+                           n_chunks)

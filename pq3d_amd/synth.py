@@ -250,6 +250,67 @@ def instseg_inputs(seed: int = 5, P=(2000,), S: int = 64, Q: int = 24, C: int = 
                 voxel_to_full_maps=v2f_l, segment_to_full_maps=s2f_l, raw_coordinates=xyz_l)
 
 
+def instseg_voxel_coordinates(inp, lattice: float = 0.1, cut_segments: int = 2, shift: float = 4.0):
+    """Voxel coordinates for the DBSCAN option of the instance-prediction step from an instseg_inputs dict: one
+    representative point per voxel (its lowest point index, as features[unique_map] keeps one row per voxel), snapped to a
+    `lattice` grid (squared distances are then multiples of lattice^2, away from the boundary eps^2 = 0.9025 for lattice
+    0.1).  In each scene the voxels of the first `cut_segments` segments with >= 4 voxels are cut in two: every second one is
+    moved by `shift` along x, so a component boundary splits those segments.  Returns a list of [V_b, 3] fp32 CPU tensors."""
+    out = []
+    for b in range(len(inp["voxel2segment"])):
+        v2s, v2f = inp["voxel2segment"][b].numpy(), inp["voxel_to_full_maps"][b].numpy()
+        V = v2s.shape[0]
+        rep = np.full(V, v2f.shape[0], np.int64)
+        np.minimum.at(rep, v2f, np.arange(v2f.shape[0]))
+        xyz = inp["raw_coordinates"][b].numpy().astype(np.float64)[rep]
+        ids, cnt = np.unique(v2s, return_counts=True)
+        for s in ids[cnt >= 4][:cut_segments]:
+            vs = np.nonzero(v2s == s)[0]
+            xyz[vs[1::2], 0] += shift
+        out.append(torch.from_numpy((np.round(xyz / lattice) * lattice).astype(np.float32)))
+    return out
+
+
+def instseg_room(seed: int = 0, V: int = 100_000, Q: int = 200, C: int = 200, voxel: float = 0.02, seg: float = 0.3,
+                 room=(8.0, 6.0, 3.0)):
+    """One synthetic room scene for the DBSCAN option at `voxel` resolution: V voxels on the floor and the four walls of a
+    room, one point per voxel, segments = `seg`-sized patches of a surface; query q's mask logits are positive on the
+    segments within 0.4-1.2 m of one or two random surface centres (two blobs: split by DBSCAN); class logits as
+    instseg_inputs.  Returns an instseg_inputs-style dict with B = 1 plus voxel_coordinates."""
+    r = np.random.default_rng([seed, 4711])
+    X, Y, Z = room
+    areas = np.array([X * Y, X * Z, X * Z, Y * Z, Y * Z])
+    face = r.choice(5, V, p=areas / areas.sum())
+    u, w = r.random(V), r.random(V)
+    xyz = np.zeros((V, 3))
+    xyz[face == 0] = np.stack([u * X, w * Y, 0 * u], 1)[face == 0]
+    xyz[face == 1] = np.stack([u * X, 0 * u, w * Z], 1)[face == 1]
+    xyz[face == 2] = np.stack([u * X, 0 * u + Y, w * Z], 1)[face == 2]
+    xyz[face == 3] = np.stack([0 * u, u * Y, w * Z], 1)[face == 3]
+    xyz[face == 4] = np.stack([0 * u + X, u * Y, w * Z], 1)[face == 4]
+    xyz = np.round(xyz / voxel) * voxel
+    cellk = np.floor(xyz / seg).astype(np.int64)
+    key = (face * 1000 + cellk[:, 0]) * 1000000 + cellk[:, 1] * 1000 + cellk[:, 2]
+    _, v2s = np.unique(key, return_inverse=True)
+    S = int(v2s.max()) + 1
+    cen = np.zeros((S, 3))
+    np.add.at(cen, v2s, xyz)
+    cen /= np.bincount(v2s, minlength=S)[:, None]
+    masks = np.full((S, Q), -3.0, np.float32)
+    for q in range(Q):
+        for k in range(1 + int(r.random() < 0.5)):
+            c = xyz[r.integers(0, V)]
+            rad = r.uniform(0.4, 1.2)
+            near = np.linalg.norm(cen - c, axis=1) < rad
+            masks[near, q] = r.uniform(0.5, 4.0, int(near.sum())).astype(np.float32)
+    logits = r.standard_normal((1, Q, C + 1)).astype(np.float32) * 2.0
+    t = lambda a: [torch.from_numpy(a)]
+    return dict(pred_logits=torch.from_numpy(logits), pred_masks=torch.from_numpy(masks[None]),
+                voxel2segment=t(v2s.astype(np.int64)), voxel_to_full_maps=t(np.arange(V, dtype=np.int64)),
+                segment_to_full_maps=t(v2s.astype(np.int64)), raw_coordinates=t(xyz.astype(np.float32)),
+                voxel_coordinates=t(xyz.astype(np.float32)))
+
+
 def instseg_ap_scene(seed: int, P: int = 3000, K: int = 24, G: int = 12, labels=(3, 5, 7, 9, 14), invalid_labels=(1, 2),
                      void_frac: float = 0.15, min_inst: int = 20):
     """One synthetic scene for mask AP: per-point GT ids (label * 1000 + instance, 0 = unlabeled; a share of the void

@@ -1003,6 +1003,21 @@ typedef struct {
 int pq3d_mask_cost_prep(const pq3d_mask_prep_desc* d, void* stream);
 int32_t pq3d_mask_cost_nsplit(int32_t Ns);
 int pq3d_match_cost(const pq3d_match_cost_desc* d, void* stream);
+/* pq3d_lsap_batched: G independent exact linear sum assignments in one launch (the matcher's Hungarian step on the device;
+ * csrc/lsap.hip).  Matrix g is the leading n_rows[g] x n_cols[g] block of cost[g] (fp32, row r at cost + (g*R + r)*ld,
+ * ld >= Cmax); n_rows / n_cols are device arrays [G] (NULL: R / Cmax for every matrix), so the launch can be captured.
+ * The result is exactly scipy.optimize.linear_sum_assignment on the block widened to float64 (rectangular_lsap.cpp, Crouse's
+ * shortest augmenting path; one 64-lane wave per matrix, see csrc/lsap.hip for the column-selection rule).
+ * Outputs, M = min(R, Cmax): row_idx / col_idx [G, M] int32 (pairs in scipy's order: ascending rows), n_match [G] =
+ * min(n_rows, n_cols) (0 on error), err [G]: 0 ok, PQ3D_LSAP_INVALID (NaN or -inf entry), PQ3D_LSAP_INFEASIBLE (no complete
+ * assignment of finite cost), PQ3D_LSAP_BAD_SIZE (n_rows / n_cols outside [0, R] / [0, Cmax]).  Slots past n_match are 0.
+ * Bounds: 1 <= R, Cmax <= PQ3D_LSAP_MAX_DIM. */
+#define PQ3D_LSAP_MAX_DIM 1024
+#define PQ3D_LSAP_INVALID 1
+#define PQ3D_LSAP_INFEASIBLE 2
+#define PQ3D_LSAP_BAD_SIZE 3
+int pq3d_lsap_batched(const float* cost, int32_t G, int32_t R, int32_t Cmax, int64_t ld, const int32_t* n_rows,
+                      const int32_t* n_cols, int32_t* row_idx, int32_t* col_idx, int32_t* n_match, int32_t* err, void* stream);
 int pq3d_matched_mask_grad(const pq3d_mask_grad_desc* d, void* stream);
 int pq3d_cross_entropy_fwd(const pq3d_ce_desc* d, void* stream);
 /* loss[layer] = sum_r row_loss / kept rows (F.cross_entropy reduction='mean' with ignore_index) [+ addend[layer]: the other

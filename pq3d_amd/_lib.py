@@ -308,6 +308,7 @@ _SIGS = {
                    C.c_void_p, C.c_void_p],
     "pq3d_mask_cost_prep": [C.POINTER(MaskPrepDesc), C.c_void_p],
     "pq3d_mask_cost_nsplit": [C.c_int32],
+    "pq3d_lsap_batched": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7,
     "pq3d_match_cost": [C.POINTER(MatchCostDesc), C.c_void_p],
     "pq3d_matched_mask_grad": [C.POINTER(MaskGradDesc), C.c_void_p],
     "pq3d_cross_entropy_fwd": [C.POINTER(CeDesc), C.c_void_p],

@@ -7,7 +7,11 @@ Where the reference loops over scenes and layers with a dozen torch ops each ((L
 each followed by a device->host copy), this runs three launches for the cost matrices of ALL layers and scenes
 (include/pq3d_hip.h: prep, one grouped + batched fp32 MFMA GEMM, cost), ONE device->host copy, the assignments on
 the host (scipy, as the reference), then the losses as gathers of the already computed cost entries plus one
-gradient launch and two cross-entropy launches.  No CPU fallback for the device part."""
+gradient launch and two cross-entropy launches.  No CPU fallback for the device part.
+
+``SetCriterion(..., matching="device")`` runs the assignments on the device instead (pq3d_amd/lsap.py: one launch for all
+layers and scenes, exactly scipy's result): the forward then makes no device-to-host transfer, and with padded targets
+(``SetCriterion.pad_targets``) decoder + criterion + backward can be captured into one graph."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,6 +24,7 @@ from scipy.optimize import linear_sum_assignment
 from torch.autograd import Function
 
 from . import _lib as L
+from .lsap import check_errors, linear_sum_assignment_batched
 
 
 class HungarianMatcher(nn.Module):
@@ -50,6 +55,21 @@ def _targets_to_device(instance_labels: Sequence[torch.Tensor], segment_masks: S
     T = T.to(device)
     return T, lab.to(device), torch.tensor(seg_len, dtype=torch.int32, device=device), \
         torch.tensor(n_inst, dtype=torch.int32, device=device), n_inst, T.sum(-1)
+
+
+class PaddedTargets:
+    """Targets of one batch at a fixed ``max_instances`` (Nt), all device tensors: T [B, Nt, Ns] fp32 0/1 masks,
+    labels [B, Nt] int64 (0 past n_inst), seg_len [B] int32, n_inst_dev [B] int32, t_sum [B, Nt] fp32 (= T.sum(-1)).
+    ``copy_`` fills a static instance (the buffers a captured graph reads) from another batch of the same shapes."""
+    __slots__ = ("T", "labels", "seg_len", "n_inst_dev", "t_sum")
+
+    def __init__(self, T, labels, seg_len, n_inst_dev, t_sum):
+        self.T, self.labels, self.seg_len, self.n_inst_dev, self.t_sum = T, labels, seg_len, n_inst_dev, t_sum
+
+    def copy_(self, other: "PaddedTargets") -> "PaddedTargets":
+        for k in self.__slots__:
+            getattr(self, k).copy_(getattr(other, k))
+        return self
 
 
 def _costs(masks, logits, T, labels, seg_len, n_inst_dev, t_sum, w, ignore_label):
@@ -101,6 +121,9 @@ class _SetCriterionFn(Function):
         m = crit.matcher
         w = (float(m.cost_class), float(m.cost_mask), float(m.cost_dice))
         cost_all, keep = _costs(masks, logits, T, labels, seg_len, n_inst_dev, t_sum, w, m.ignore_label)
+        if crit.matching == "device":
+            return _SetCriterionFn._device_tail(ctx, crit, cost_all, keep, masks, logits, T, labels, seg_len, n_inst_dev,
+                                                n_inst, t_sum, n_layers, preds)
         host = cost_all[:, 0].cpu().numpy()            # the ONE device->host copy of the step: [layers, B, Nq, Nt]
         Nm = max(min(Nq, max(n_inst)), 1)
         q_idx = np.zeros((n_layers, B, Nm), dtype=np.int32)
@@ -148,6 +171,56 @@ class _SetCriterionFn(Function):
         return losses
 
     @staticmethod
+    def _device_tail(ctx, crit, cost_all, keep, masks, logits, T, labels, seg_len, n_inst_dev, n_inst, t_sum, n_layers,
+                     preds):
+        """matching="device": the assignments of every (layer, scene) in one launch and the CE targets by a scatter, with
+        no device-to-host transfer.  Same gathers and kernels as the host mode on the same indices."""
+        B, Ns, Nq = masks[0].shape
+        Nt, dev, Ccls = T.shape[1], T.device, logits[0].shape[-1]
+        Nm = min(Nq, Nt)
+        cmat = cost_all[:, 0].reshape(n_layers * B, Nq, Nt)                    # matrix g = (layer g // B, scene g % B)
+        row, col, nmd, err = linear_sum_assignment_batched(cmat, None, n_inst_dev.repeat(n_layers))
+        q_idx_d, t_idx_d = row.view(n_layers, B, Nm), col.view(n_layers, B, Nm)
+        n_match_d = nmd.view(n_layers, B)
+        bad = err.view(n_layers, B) != 0
+        valid = torch.arange(Nm, device=dev)[None, None, :] < n_match_d[:, :, None]             # [layers, B, Nm]
+        lidx = torch.arange(n_layers, device=dev)[:, None, None].expand(n_layers, B, Nm)
+        bidx = torch.arange(B, device=dev)[None, :, None].expand(n_layers, B, Nm)
+        qi, ti = q_idx_d.long(), t_idx_d.long()
+        nmf = n_match_d.float().clamp(min=1.0)
+        pair = cost_all[:, 1:3][lidx, :, bidx, qi, ti] * valid[..., None]                        # [layers, B, Nm, 2]
+        per = pair.sum(2) / nmf[..., None]                                                      # [layers, B, 2]
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        losses = torch.zeros(n_layers, 3, dtype=torch.float32, device=dev)
+        losses[:, 1:3] = torch.where(bad[..., None], nan, per).mean(1)      # a failed matrix: NaN losses of its layer
+        # classification targets: matched queries take their target's label, the rest the no-object class; unmatched
+        # slots scatter into a spare column Nq that is dropped (no boolean-mask indexing, no sync)
+        tgt = torch.full((n_layers, B, Nq + 1), crit.num_classes, dtype=torch.int64, device=dev)
+        tgt.scatter_(2, torch.where(valid, qi, torch.full_like(qi, Nq)), labels[bidx, ti])
+        tgt = tgt[..., :Nq].contiguous()
+        row_loss = torch.empty(n_layers, B * Nq, dtype=torch.float32, device=dev)
+        lse = torch.empty_like(row_loss)
+        ce = L.CeDesc()
+        ce.layers, ce.C, ce.R, ce.ignore_index = n_layers, Ccls, B * Nq, crit.ignore_label
+        for l in range(n_layers):
+            ce.logits[l] = L.ptr(logits[l])
+        ce.target, ce.row_loss, ce.lse = L.ptr(tgt), L.ptr(row_loss), L.ptr(lse)
+        L.check(L.lib().pq3d_cross_entropy_fwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_fwd")
+        cnt = (tgt != crit.ignore_label).sum((1, 2)).clamp(min=1).float()
+        losses[:, 0] = torch.where(bad.any(1), nan, row_loss.sum(1) / cnt)
+        ctx.crit, ctx.n_layers, ctx.keep = crit, n_layers, keep
+        ctx.masks, ctx.logits, ctx.tgt, ctx.lse, ctx.cnt = masks, logits, tgt, lse, cnt
+        ctx.targets = (T, seg_len, t_sum, q_idx_d, t_idx_d, n_match_d, nmf, Nm)
+        ctx.in_dtypes = [p.dtype for p in preds]
+        crit._last_err = err
+        if n_inst is None:      # padded targets: the per-scene counts stay on the device
+            crit._last_indices = [(qi[l], ti[l], n_match_d[l]) for l in range(n_layers)]
+        else:
+            crit._last_indices = [[(qi[l, b, :min(Nq, n_inst[b])], ti[l, b, :min(Nq, n_inst[b])]) for b in range(B)]
+                                  for l in range(n_layers)]
+        return losses
+
+    @staticmethod
     def backward(ctx, g):
         T, seg_len, t_sum, q_idx_d, t_idx_d, n_match_d, nmf, Nm = ctx.targets
         n_layers = ctx.n_layers
@@ -178,25 +251,77 @@ class _SetCriterionFn(Function):
 
 class SetCriterion(nn.Module):
     """criterion.py:95-270: forward(predictions_mask, predictions_class, instance_labels, segment_masks) ->
-    (losses dict with 'loss_ce', 'loss_mask', 'loss_dice' and the '_i' auxiliary copies, indices of the last layer)."""
+    (losses dict with 'loss_ce', 'loss_mask', 'loss_dice' and the '_i' auxiliary copies, indices of the last layer).
 
-    def __init__(self, num_classes, matcher, weight_dict, losses, num_points, class_weights, ignore_label):
+    ``matching``: "host" (scipy per (layer, scene), the reference's path) or "device" (pq3d_amd/lsap.py, the same
+    assignments with no device-to-host transfer; the last layer's indices are then int64 device tensors, and a failed
+    assignment makes its layer's losses NaN -- ``check()`` raises scipy's error).  Device mode also takes
+    ``targets=SetCriterion.pad_targets(...)`` instead of the two lists, which makes the step capturable; the indices are
+    then (q_idx [B, Nm], t_idx [B, Nm], n_match [B]) device tensors with pairs k < n_match[b] valid."""
+
+    def __init__(self, num_classes, matcher, weight_dict, losses, num_points, class_weights, ignore_label,
+                 matching: str = "host"):
         super().__init__()
         if num_points != -1 or class_weights != -1:
             raise NotImplementedError("only num_points = -1, class_weights = -1 (configs/instseg_sceneverse.yaml:163-168)")
+        if matching not in ("host", "device"):
+            raise ValueError(f"matching must be 'host' or 'device', got {matching!r}")
         self.num_classes, self.matcher, self.weight_dict, self.losses = num_classes, matcher, weight_dict, list(losses)
         self.num_points, self.class_weights, self.ignore_label = num_points, class_weights, ignore_label
+        self.matching = matching
         self._last_indices = None
+        self._last_err = None
 
-    def forward(self, predictions_mask, predictions_class, instance_labels, segment_masks):
+    @staticmethod
+    def pad_targets(instance_labels: Sequence[torch.Tensor], segment_masks: Sequence[torch.Tensor], Ns: int,
+                    max_instances: int, device=None) -> PaddedTargets:
+        """The targets of one batch as device tensors at a fixed ``max_instances`` (host loop; call it outside a capture
+        and ``copy_`` the result into the static targets a captured step reads).  Scenes may have 0 instances."""
+        B = len(segment_masks)
+        if B < 1 or len(instance_labels) != B:
+            raise ValueError("one instance_labels and one segment_masks entry per scene")
+        n_inst = [int(m.shape[0]) for m in segment_masks]
+        if max_instances < 1 or max(n_inst) > max_instances:
+            raise ValueError(f"max_instances = {max_instances} must be >= 1 and >= the largest instance count {max(n_inst)}")
+        if max(int(m.shape[1]) for m in segment_masks) > Ns:
+            raise ValueError("target masks have more segments than Ns")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        T = torch.zeros(B, max_instances, Ns, dtype=torch.float32)
+        lab = torch.zeros(B, max_instances, dtype=torch.int64)
+        for b in range(B):
+            T[b, :n_inst[b], :segment_masks[b].shape[1]] = segment_masks[b].float().cpu()
+            lab[b, :n_inst[b]] = instance_labels[b].cpu()
+        T = T.to(dev)
+        seg_len = torch.tensor([int(m.shape[1]) for m in segment_masks], dtype=torch.int32, device=dev)
+        return PaddedTargets(T, lab.to(dev), seg_len, torch.tensor(n_inst, dtype=torch.int32, device=dev), T.sum(-1))
+
+    def check(self) -> None:
+        """Raise scipy's ValueError if an assignment of the last device-mode forward failed (reads the error codes)."""
+        if self._last_err is not None:
+            check_errors(self._last_err)
+
+    def forward(self, predictions_mask, predictions_class, instance_labels=None, segment_masks=None, targets=None):
         n = len(predictions_mask)
         # reference order: the LAST prediction is the main output, the others are the auxiliary '_i' losses
         order = [n - 1] + list(range(n - 1))
         masks = [predictions_mask[i] for i in order]
         logits = [predictions_class[i] for i in order]
         dev = masks[0].device
-        T, labels, seg_len, n_inst_dev, n_inst, t_sum = _targets_to_device(instance_labels, segment_masks,
-                                                                         masks[0].shape[1], dev)
+        if targets is not None:
+            if self.matching != "device":
+                raise ValueError("padded targets need SetCriterion(..., matching='device')")
+            if not isinstance(targets, PaddedTargets):
+                raise ValueError("targets must come from SetCriterion.pad_targets")
+            B, Ns = masks[0].shape[:2]
+            if targets.T.shape[0] != B or targets.T.shape[2] != Ns or targets.T.device != dev:
+                raise ValueError(f"padded targets {tuple(targets.T.shape)} on {targets.T.device} do not match predictions "
+                                 f"[B = {B}, Ns = {Ns}] on {dev}")
+            T, labels, seg_len, n_inst_dev, t_sum = (targets.T, targets.labels, targets.seg_len, targets.n_inst_dev,
+                                                     targets.t_sum)
+            n_inst = None
+        else:
+            T, labels, seg_len, n_inst_dev, n_inst, t_sum = _targets_to_device(instance_labels, segment_masks,
+                                                                             masks[0].shape[1], dev)
         out = _SetCriterionFn.apply(self, T, labels, seg_len, n_inst_dev, n_inst, t_sum, n, *masks, *logits)
         names = {"labels": [(0, "loss_ce")], "masks": [(1, "loss_mask"), (2, "loss_dice")]}
         losses: Dict[str, torch.Tensor] = {}
@@ -212,7 +337,7 @@ class InstSegLoss(nn.Module):
     """optim/loss/instseg_loss.py:9-52: criterion_type 'set' (Hungarian matching, stage 1) or 'direct' (ground-truth
     masks, query i <-> instance i, configs/instseg_sceneverse_gt.yaml:160)."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, matching: str = "host"):
         super().__init__()
         self.cfg = cfg
         loss_cfg = cfg.model.get(self.__class__.__name__)
@@ -221,7 +346,8 @@ class InstSegLoss(nn.Module):
         matcher = HungarianMatcher(**dict(loss_cfg.matcher))
         self.weight_dict = {"loss_ce": matcher.cost_class, "loss_mask": matcher.cost_mask, "loss_dice": matcher.cost_dice}
         if self.criterion_type == "set":
-            self.set_criterion = SetCriterion(matcher=matcher, weight_dict=self.weight_dict, **dict(loss_cfg.criterion))
+            self.set_criterion = SetCriterion(matcher=matcher, weight_dict=self.weight_dict, matching=matching,
+                                              **dict(loss_cfg.criterion))
         else:   # instseg_loss.py:34-35: DirectCriterion(**loss_cfg.criterion) swallows the set criterion's other keys
             self.direct_criterion = DirectCriterion(**dict(loss_cfg.criterion))
 

@@ -8,6 +8,8 @@ from typing import Optional, Sequence
 
 import torch
 
+from .profiler import timed
+
 F32, BF16, BF16X3 = 0, 1, 2
 ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "add": 3, "planes": 4}
 MAXG = 32
@@ -413,6 +415,42 @@ def ptr(t: Optional[torch.Tensor]):
     return t.data_ptr()
 
 
+def parr(ts):
+    """ctypes array of the device pointers of a list of tensors (None entries stay NULL)."""
+    return (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+
+
+_current_stream = stream    # (call's keyword is named stream too)
+_ENTRY = {}     # entry point -> (function, positions taking a device pointer, positions taking a descriptor by reference)
+
+
+def _entry(name: str):
+    fn, sig = getattr(lib(), name), _SIGS[name]
+    if name in _RET64 or not sig or sig[-1] is not C.c_void_p:
+        raise Pq3dError(f"{name} is not a launch entry point (status return, stream last): use lib() directly")
+    pos = lambda pred: tuple(i for i, t in enumerate(sig[:-1]) if pred(t))
+    e = _ENTRY[name] = (fn, pos(lambda t: t is C.c_void_p),
+                        pos(lambda t: isinstance(getattr(t, "_type_", None), type) and issubclass(t._type_, C.Structure)))
+    return e
+
+
+def call(name: str, *args, work=None, stream=None) -> None:
+    """The one way into a launch entry point: lib().<name>(*args, stream), then check().  A torch.Tensor argument is passed as
+    ptr(t) (so a CPU tensor raises before the library is entered), a ctypes.Structure by reference; None, numbers and ctypes
+    arrays go through as they are (lists of tensors: parr).  ``stream`` defaults to torch's current stream.
+    ``work=(key, flops, bytes)`` times the call under profiler.KernelTimer as (name, key)."""
+    fn, ptrs, by_ref = _ENTRY.get(name) or _entry(name)
+    a = list(args)
+    for i in ptrs:
+        if isinstance(a[i], torch.Tensor):
+            a[i] = ptr(a[i])
+    for i in by_ref:
+        if isinstance(a[i], C.Structure):
+            a[i] = C.byref(a[i])
+    a.append(_current_stream() if stream is None else stream)
+    check(fn(*a) if work is None else timed(name, *work, fn, *a), name)
+
+
 def _fill(arr, tensors: Optional[Sequence[Optional[torch.Tensor]]]):
     if tensors is None:
         return
@@ -446,10 +484,8 @@ def gemm(*, M, N, K, A, B, Cs, ct, lda, ldb, ldc, A2=None, B2=None, bias=None, C
     _fill(d.C2, C2); _fill(d.aux, aux); _fill(d.row_mask, row_mask); _fill(d.colsum, colsum)
     d.row_scale, d.row_fill_flag, d.mask_out = ptr(row_scale), ptr(row_fill_flag), ptr(mask_out)
     set_drop(d.drop, drop)
-    from .profiler import timed
     nb = (M * K * (2 if d.dtA else 4) + N * K * (2 if d.dtB else 4)) * len(A) * batch + \
         M * N * (2 if d.dtC else 4) * (len(A) // max(kconcat, 1)) * batch
     key = f"M{M}N{N}K{K}g{len(A)}b{batch}{'T' if transA else 'N'}{'T' if transB else 'N'}" \
           f"{'k%d' % kconcat if kconcat else ''}{'s%d' % splitk if splitk > 1 else ''}ct{ct}"
-    check(timed("pq3d_gemm", key, 2.0 * M * N * K * len(A) * batch, nb, lib().pq3d_gemm, C.byref(d), stream()),
-          "pq3d_gemm")
+    call("pq3d_gemm", d, work=(key, 2.0 * M * N * K * len(A) * batch, nb))

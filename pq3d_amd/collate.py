@@ -42,8 +42,7 @@ class RaggedBatch:
         out = torch.empty(B, Lmax, *tail, dtype=v.dtype, device=v.device)
         mask = torch.empty(B, Lmax, dtype=torch.bool, device=v.device) if return_mask else None
         pb = _pad_bytes(v.dtype, pad)
-        L.check(L.lib().pq3d_pad_sequence(L.ptr(v) if v.numel() else None, L.ptr(self.offsets), L.ptr(out), L.ptr(mask), B,
-                                          Lmax, D, v.element_size(), C.cast(pb, C.c_void_p), L.stream()), "pq3d_pad_sequence")
+        L.call("pq3d_pad_sequence", v if v.numel() else None, self.offsets, out, mask, B, Lmax, D, v.element_size(), C.cast(pb, C.c_void_p))
         return (out, mask) if return_mask else out
 
 
@@ -71,7 +70,6 @@ def pad_sequence_2d(sequence_list: List[torch.Tensor], max_height=None, max_widt
     out = torch.empty(B, H, W, *tail, dtype=dt, device=dev)
     mask = torch.empty(B, H, W, dtype=torch.bool, device=dev) if return_mask else None
     pb = _pad_bytes(dt, pad)
-    L.check(L.lib().pq3d_pad_sequence_2d(L.ptr(flat) if flat.numel() else None, L.ptr(offsets), L.ptr(hd), L.ptr(wd),
-                                         L.ptr(out), L.ptr(mask), B, H, W, D, flat.element_size(),
-                                         C.cast(pb, C.c_void_p), L.stream()), "pq3d_pad_sequence_2d")
+    L.call("pq3d_pad_sequence_2d", flat if flat.numel() else None, offsets, hd, wd, out, mask, B, H, W, D, flat.element_size(),
+           C.cast(pb, C.c_void_p))
     return (out, mask) if return_mask else out

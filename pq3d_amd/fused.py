@@ -20,7 +20,6 @@ sublayer step: `_DecoderForward.run` hoists the layer-invariant work and walks t
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 from collections import namedtuple
@@ -33,7 +32,6 @@ from . import _lib as L
 from . import ops, wgrad
 from .wgrad import _colsum_acc  # noqa: F401  (importable from fused as before: tests/test_gpu_ops.py)
 from ._lib import BF16
-from .profiler import timed
 
 MAXG = L.MAXG
 
@@ -154,8 +152,7 @@ def _mh_forward(spec, x, keys, inv_den, seg_pad, rec, call):
         cls = cls_raw
         if mh._foc_cols.numel():
             cls = torch.empty_like(cls_raw)
-            L.check(L.lib().pq3d_fill_cols(L.ptr(cls_raw), L.ptr(cls), R, C_, L.ptr(mh._foc_cols), mh._foc_cols.numel(),
-                                           float("-inf"), L.stream()), "pq3d_fill_cols")
+            L.call("pq3d_fill_cols", cls_raw, cls, R, C_, mh._foc_cols, mh._foc_cols.numel(), float("-inf"))
         qm = torch.empty(Mm, B, Nq, d, dtype=ad, device=x.device)
         L.gemm(M=R, N=d, K=d, A=[x] * Mm, B=[mp.q_proj.weight.detach() for mp in mps],
                bias=[mp.q_proj.bias.detach() for mp in mps], Cs=[qm[m] for m in range(Mm)], ct=ct, lda=d, ldb=d, ldc=d)
@@ -179,8 +176,7 @@ def _ln_fwd(x, os_, gammas, betas, eps, coef, rows_per_scene, out_dtype=torch.fl
     d = ops._ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, drop)
     d.sum_branches, d.osum = int(sum_branches), L.ptr(osum)
     nb = (M + 1 + (x is not None)) * R * dm * 4.0
-    L.check(timed("pq3d_add_ln_fwd", f"R{R}d{dm}M{M}", 0.0, nb, L.lib().pq3d_add_ln_fwd, C.byref(d), L.stream()),
-            "pq3d_add_ln_fwd")
+    L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
     return y, mean, rstd
 
 
@@ -205,8 +201,7 @@ def _ln_bwd(x, os_, gammas, betas, eps, coef, rows_per_scene, mean, rstd, dy, dg
     for m in range(1 if sum_branches else M):
         d.d_o[m], d.dgamma[m], d.dbeta[m] = L.ptr(d_o[m]), L.ptr(dgs[m]), L.ptr(dbs[m])
     nb = (3 * M + 1 + (x is not None)) * R * dm * 4.0
-    L.check(timed("pq3d_add_ln_bwd", f"R{R}d{dm}M{M}", 0.0, nb, L.lib().pq3d_add_ln_bwd, C.byref(d), L.stream()),
-            "pq3d_add_ln_bwd")
+    L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
     return dx, d_o
 
 
@@ -237,15 +232,13 @@ def _attn(q, k, v, o, lse, H, ct, zero_attn, kpm=None, mask=None, row_open=None,
             d.ksplit, d.ws = ks, L.ptr(d._ws_keepalive)
     key = f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}" + ("m3" if mask is not None else "")
     if bwd is None:
-        L.check(timed("pq3d_attn_fwd", key, 4.0 * B * Lq * Lk * dm, (q.numel() * 2 + k.numel() * 2) * q.element_size(),
-                      L.lib().pq3d_attn_fwd, C.byref(d), L.stream()), "pq3d_attn_fwd")
+        L.call("pq3d_attn_fwd", d, work=(key, 4.0 * B * Lq * Lk * dm, (q.numel() * 2 + k.numel() * 2) * q.element_size()))
     else:
         d.dout, d.dq, d.dk, d.dv, d.delta, d.dbias = map(L.ptr, bwd)
         if proj_dout is not None:
             d.proj.mode, d.proj.dm, d.proj.x = 2, dm, L.ptr(proj_dout[0])
             d.proj.w[0] = L.ptr(proj_dout[1])
-        L.check(timed("pq3d_attn_bwd", key, 8.0 * B * Lq * Lk * dm, (q.numel() * 3 + k.numel() * 4) * q.element_size(),
-                      L.lib().pq3d_attn_bwd, C.byref(d), L.stream()), "pq3d_attn_bwd")
+        L.call("pq3d_attn_bwd", d, work=(key, 8.0 * B * Lq * Lk * dm, (q.numel() * 3 + k.numel() * 4) * q.element_size()))
 
 
 def sa_fold_ok(ct, B, H, L_, dm, drop, df, W) -> bool:
@@ -434,8 +427,7 @@ class _DecoderBackward(_DecoderPass):
             dcl = dc.contiguous()
             if mh._foc_cols.numel():
                 t = torch.empty_like(dcl)
-                L.check(L.lib().pq3d_fill_cols(L.ptr(dcl), L.ptr(t), R, C_, L.ptr(mh._foc_cols),
-                                               mh._foc_cols.numel(), 0.0, L.stream()), "pq3d_fill_cols")
+                L.call("pq3d_fill_cols", dcl, t, R, C_, mh._foc_cols, mh._foc_cols.numel(), 0.0)
                 dcl = t
             dh2 = torch.empty(B, Nq, Hd, dtype=torch.float32, device=dev)
             L.gemm(M=R, N=Hd, K=C_, A=[dcl], B=[c4.weight.detach()], Cs=[dh2], ct=ct, lda=C_, ldb=Hd, ldc=Hd, transB=True)
@@ -590,9 +582,8 @@ class _DecoderBackward(_DecoderPass):
         pl, H, B, Nq, sb_queue = self.pl, self.H, self.B, self.Nq, self.sb_queue
         for i0 in range(0, len(sb_queue), MAXG):
             chunk = sb_queue[i0:i0 + MAXG]
-            arrs = [(C.c_void_p * len(chunk))(*[L.ptr(t[k]) for t in chunk]) for k in range(5)]
-            L.check(L.lib().pq3d_spatial_bias_bwd_grouped(L.ptr(pl), *arrs, len(chunk), B, H, Nq, L.stream()),
-                    "pq3d_spatial_bias_bwd_grouped")
+            arrs = [L.parr([t[k] for t in chunk]) for k in range(5)]
+            L.call("pq3d_spatial_bias_bwd_grouped", pl, *arrs, len(chunk), B, H, Nq)
         del sb_queue[:]
 
     def ffn(self, rec, layer, dx):
@@ -879,9 +870,8 @@ class _DecoderBackward(_DecoderPass):
                 kws = [mp.k_proj.weight.detach() for mp in list(spec.mh.mask_pred_list)[:spec.mh_count]]
                 if d % 32 == 0 and ad == torch.bfloat16 and len(kws) <= MAXG and all(w_.is_contiguous() and w_.shape == (d, d) for w_ in kws):
                     kT, kS = torch.empty(2, len(kws), d, d, dtype=ad, device=dev)
-                    L.check(L.lib().pq3d_cast_transpose(ops._parr(kws), ops._parr([kS[m_] for m_ in range(len(kws))]),
-                                                        ops._parr([kT[m_] for m_ in range(len(kws))]), len(kws), d, d, L.stream()),
-                            "pq3d_cast_transpose")
+                    L.call("pq3d_cast_transpose", L.parr(kws), L.parr([kS[m_] for m_ in range(len(kws))]),
+                           L.parr([kT[m_] for m_ in range(len(kws))]), len(kws), d, d)
                 else:
                     kT = torch.stack(kws).transpose(1, 2).contiguous().to(ad)
         # d source_u = sum over the (application, memory) pairs that read it of (dK Wk + dV Wv) [+ mask-head key path]
@@ -998,8 +988,7 @@ class _DecoderForward(_DecoderPass):
             if kv3:   # both planes of (feat + pos) and feat in one launch; the K / V weights' residual planes join it below
                 kvin_lo = torch.empty(2, U, B, Ns, d, dtype=ad, device=dev)
             else:
-                L.check(L.lib().pq3d_add_cast(ops._parr(f_srcs), ops._parr(f_adds), ops._parr(f_outs), 2 * U, L.BF16, B * Ns * d,
-                                              L.stream()), "pq3d_add_cast")
+                L.call("pq3d_add_cast", L.parr(f_srcs), L.parr(f_adds), L.parr(f_outs), 2 * U, L.BF16, B * Ns * d)
             kin, vin, kin2 = [kvin[0, u] for u in range(U)], [kvin[1, u] for u in range(U)], [None] * U
         else:
             kin, vin, kin2 = feats, feats, [pos] * U
@@ -1017,12 +1006,11 @@ class _DecoderForward(_DecoderPass):
                 # the same launch also leaves the transposed blocks [l, m, t][k_in][n_out] the backward's input-gradient
                 # products read (plain NT products on W^T: the 128x128-tile kernel's layout)
                 wkvT = torch.empty(Ln, M, 2, d, d, dtype=ad, device=dev)
-                L.check(L.lib().pq3d_cast_transpose(ops._parr(w_srcs), ops._parr(w_outs),
-                                                    ops._parr([wkvT[i, j] for i in range(Ln) for j in range(M)]),
-                                                    len(w_srcs), 2 * d, d, L.stream()), "pq3d_cast_transpose")
+                L.call("pq3d_cast_transpose", L.parr(w_srcs), L.parr(w_outs),
+                       L.parr([wkvT[i, j] for i in range(Ln) for j in range(M)]), len(w_srcs), 2 * d, d)
             else:
-                L.check(L.lib().pq3d_add_cast(ops._parr(w_srcs), ops._parr([None] * len(w_srcs)), ops._parr(w_outs), len(w_srcs),
-                                              L.BF16, 2 * d * d, L.stream()), "pq3d_add_cast")
+                L.call("pq3d_add_cast", L.parr(w_srcs), L.parr([None] * len(w_srcs)), L.parr(w_outs), len(w_srcs), L.BF16,
+                       2 * d * d)
         self.wkv, self.wkvT = wkv, wkvT
         self.KV_lo = KV_lo = None
         if kv3:
@@ -1095,10 +1083,8 @@ class _DecoderForward(_DecoderPass):
         fcs = [layer.self_attn.self_attn.pairwise_loc_fc for layer in self.layers]
         for i0 in range(0, Ln, MAXG):
             n_ = min(MAXG, Ln - i0)
-            L.check(L.lib().pq3d_spatial_bias_fwd_grouped(
-                L.ptr(self.pl), ops._parr([fc.weight.detach() for fc in fcs[i0:i0 + n_]]),
-                ops._parr([fc.bias.detach() for fc in fcs[i0:i0 + n_]]), ops._parr([sbias_all[i0 + k] for k in range(n_)]), n_, B, H,
-                Nq, L.stream()), "pq3d_spatial_bias_fwd_grouped")
+            L.call("pq3d_spatial_bias_fwd_grouped", self.pl, L.parr([fc.weight.detach() for fc in fcs[i0:i0 + n_]]),
+                   L.parr([fc.bias.detach() for fc in fcs[i0:i0 + n_]]), L.parr([sbias_all[i0 + k] for k in range(n_)]), n_, B, H, Nq)
 
     def cross_attn(self, app, rec, x):
         """Cross-attention over the M scene memories, 4 launches: query projections (unless the previous application's chain

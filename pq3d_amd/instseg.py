@@ -45,7 +45,6 @@ import torch
 
 from . import _lib as L
 from .ops import SegmentPlan
-from .profiler import timed
 
 SEG_CHUNK = 64           # PQ3D_INSTSEG_SEG_CHUNK
 PT_CHUNK = 256           # PQ3D_INSTSEG_PT_CHUNK
@@ -141,15 +140,13 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     n_chunks = offs_h[-1]
     offs = torch.tensor(offs_h, dtype=torch.int64).to(dev)
     logits, masks_in = pred_logits.contiguous(), pred_masks.contiguous()
-    lib, st = L.lib(), L.stream()
     i32 = dict(dtype=torch.int32, device=dev)
 
     # 1. range checks + voxels per segment (read back below, after the launches that do not depend on it)
     nvox = torch.empty(B * S, **i32)
     stats = torch.empty(2, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_instseg_check", f"B{B}V{NV}P{NP}", 0.0, NV * 8.0 + NP * 16.0 + B * S * 4.0,
-                  lib.pq3d_instseg_check, L.ptr(v2s), L.ptr(v2f), L.ptr(s2f), L.ptr(offs), B, S, NV, NP, L.ptr(nvox),
-                  L.ptr(stats), st), "pq3d_instseg_check")
+    L.call("pq3d_instseg_check", v2s, v2f, s2f, offs, B, S, NV, NP, nvox, stats,
+           work=(f"B{B}V{NV}P{NP}", 0.0, NV * 8.0 + NP * 16.0 + B * S * 4.0))
     if use_dbscan:
         xyzv = _cat(voxel_coordinates, torch.float32, "voxel_coordinates", dev)
         return _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h, stats, B, S, Q, C1, K, kall,
@@ -161,15 +158,12 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     if ragged:      # the filter alone: dropped queries' candidates left out of the select (query order kept: no compaction)
         qvalid, kout = torch.empty(B * Q, **i32), torch.empty(B, **i32)
         seg = torch.arange(0, (B + 1) * Q * C_, Q * C_, dtype=torch.int64).to(dev)
-        L.check(timed("pq3d_instseg_prob", f"B{B}Q{Q}C{C1}f", 0.0, B * Q * C1 * 8.0, lib.pq3d_instseg_prob, L.ptr(logits), B,
-                      Q, C1, L.ptr(prob), L.ptr(qvalid), st), "pq3d_instseg_prob")
-        L.check(timed("pq3d_instseg_topk_ragged", f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C_ * 4.0 + B * K * 12.0,
-                      lib.pq3d_instseg_topk_ragged, L.ptr(prob), L.ptr(seg), L.ptr(qvalid), B, C_, K, int(kall), Q * C_,
-                      L.ptr(sel_prob), L.ptr(sel_query), L.ptr(sel_class), L.ptr(kout), st), "pq3d_instseg_topk_ragged")
+        L.call("pq3d_instseg_prob", logits, B, Q, C1, prob, qvalid, work=(f"B{B}Q{Q}C{C1}f", 0.0, B * Q * C1 * 8.0))
+        L.call("pq3d_instseg_topk_ragged", prob, seg, qvalid, B, C_, K, int(kall), Q * C_, sel_prob, sel_query, sel_class, kout,
+               work=(f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C_ * 4.0 + B * K * 12.0))
     else:
-        L.check(timed("pq3d_instseg_topk", f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C1 * 4.0 + B * K * 12.0,
-                      lib.pq3d_instseg_topk, L.ptr(logits), B, Q, C1, K, L.ptr(prob), L.ptr(sel_prob), L.ptr(sel_query),
-                      L.ptr(sel_class), st), "pq3d_instseg_topk")
+        L.call("pq3d_instseg_topk", logits, B, Q, C1, K, prob, sel_prob, sel_query, sel_class,
+               work=(f"B{B}Q{Q}C{C1}K{K}", 0.0, B * Q * C1 * 4.0 + B * K * 12.0))
     # 3. bit table [B*S, K] (top-k order) + mask scores, sorted by score
     nsc = (S + SEG_CHUNK - 1) // SEG_CHUNK
     table = torch.empty(B * S, K, dtype=torch.float32, device=dev)
@@ -177,10 +171,8 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
     scores = torch.empty(B, K, dtype=torch.float32, device=dev)
     classes = torch.empty(B, K, dtype=torch.int64, device=dev)
     order = torch.empty(B, K, **i32)
-    L.check(timed("pq3d_instseg_scores", f"B{B}S{S}Q{Q}K{K}", 0.0, B * S * (K * 8.0 + 4.0) + B * K * 24.0,
-                  lib.pq3d_instseg_scores, L.ptr(masks_in), L.ptr(nvox), L.ptr(sel_prob), L.ptr(sel_query),
-                  L.ptr(sel_class), B, S, Q, K, L.ptr(table), L.ptr(ws), ws.numel(), L.ptr(scores), L.ptr(classes),
-                  L.ptr(order), st), "pq3d_instseg_scores")
+    L.call("pq3d_instseg_scores", masks_in, nvox, sel_prob, sel_query, sel_class, B, S, Q, K, table, ws, ws.numel(), scores, classes, order,
+           work=(f"B{B}S{S}Q{Q}K{K}", 0.0, B * S * (K * 8.0 + 4.0) + B * K * 24.0))
 
     if ragged:
         host = torch.cat((stats, kout.to(torch.int64))).cpu().tolist()     # the one device-to-host read of the call
@@ -206,13 +198,11 @@ def _vote_and_boxes(v2s, v2f, s2f, xyz, offs, offs_h, table, order, scores, clas
     """Steps 4-5 on the 0/1 table [B*S, K] whose row of point p is b*S + v2s[voff[b] + voxel_to_full_maps[p]]; scene b's
     record keeps its first Kb[b] sorted columns."""
     dev = table.device
-    lib, st = L.lib(), L.stream()
     NP = sum(P)
     # 4. vote per full-resolution segment: rows voxel2segment[voxel_to_full_maps[p]] of the table, grouped by segment_to_full_maps
     gather = torch.empty(NP, dtype=torch.int64, device=dev)
     key = torch.empty(NP, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_instseg_compose", f"B{B}P{NP}", 0.0, NP * 40.0, lib.pq3d_instseg_compose, L.ptr(v2s), L.ptr(v2f),
-                  L.ptr(s2f), L.ptr(offs), B, S, Sf, NP, L.ptr(gather), L.ptr(key), st), "pq3d_instseg_compose")
+    L.call("pq3d_instseg_compose", v2s, v2f, s2f, offs, B, S, Sf, NP, gather, key, work=(f"B{B}P{NP}", 0.0, NP * 40.0))
     out = torch.empty(NP, K, dtype=torch.bool, device=dev)
     if NP > 0:
         plan = SegmentPlan(key, B * Sf)
@@ -223,10 +213,8 @@ def _vote_and_boxes(v2s, v2f, s2f, xyz, offs, offs_h, table, order, scores, clas
     # 5. masks in sorted column order + boxes
     boxes = torch.empty(B, K, 6, dtype=torch.float32, device=dev)
     valid = torch.empty(B, K, dtype=torch.bool, device=dev)
-    L.check(timed("pq3d_instseg_expand", f"B{B}P{NP}K{K}", 0.0, NP * (K * 5.0 + 20.0) + n_chunks * K * BOX_PART_BYTES,
-                  lib.pq3d_instseg_expand, L.ptr(vsum), L.ptr(vcount), L.ptr(key), L.ptr(xyz), L.ptr(offs), L.ptr(order), B,
-                  NP, n_chunks, K, L.ptr(out), L.ptr(bws), 0 if bws is None else bws.numel(), L.ptr(boxes), L.ptr(valid), st),
-            "pq3d_instseg_expand")
+    L.call("pq3d_instseg_expand", vsum, vcount, key, xyz, offs, order, B, NP, n_chunks, K, out, bws, 0 if bws is None else bws.numel(),
+           boxes, valid, work=(f"B{B}P{NP}K{K}", 0.0, NP * (K * 5.0 + 20.0) + n_chunks * K * BOX_PART_BYTES))
     res = []
     p0 = offs_h[B + 1]
     for b in range(B):
@@ -255,18 +243,15 @@ def _fdec(code: int) -> float:
 def _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h, stats, B, S, Q, C1, K, kall, filt, eps, V, P,
                         n_chunks):
     dev = logits.device
-    lib, st = L.lib(), L.stream()
     i32 = dict(dtype=torch.int32, device=dev)
     C_ = C1 - 1
     NV = sum(V)
     # D1. coordinate bounds + non-finite flag, class probabilities (+ filter flags); read 1: flags, Sf, bounds
     bounds = torch.empty(B * 6, **i32)
-    L.check(timed("pq3d_dbscan_bounds", f"B{B}V{NV}", 0.0, NV * 12.0, lib.pq3d_dbscan_bounds, L.ptr(xyzv), L.ptr(offs), B, NV,
-                  L.ptr(bounds), L.ptr(stats), st), "pq3d_dbscan_bounds")
+    L.call("pq3d_dbscan_bounds", xyzv, offs, B, NV, bounds, stats, work=(f"B{B}V{NV}", 0.0, NV * 12.0))
     prob = torch.empty(B, Q * C_, dtype=torch.float32, device=dev)
     qvalid = torch.empty(B * Q, **i32) if filt else None
-    L.check(timed("pq3d_instseg_prob", f"B{B}Q{Q}C{C1}{'f' if filt else ''}", 0.0, B * Q * C1 * 8.0, lib.pq3d_instseg_prob,
-                  L.ptr(logits), B, Q, C1, L.ptr(prob), L.ptr(qvalid), st), "pq3d_instseg_prob")
+    L.call("pq3d_instseg_prob", logits, B, Q, C1, prob, qvalid, work=(f"B{B}Q{Q}C{C1}{'f' if filt else ''}", 0.0, B * Q * C1 * 8.0))
     host = torch.cat((stats, bounds.to(torch.int64) & 0xFFFFFFFF)).cpu().tolist()
     Sf = _check_stats(int(host[0]), int(host[1]), B)
     if NV == 0:
@@ -290,18 +275,16 @@ def _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h
         ndense += cells
     gtab = torch.tensor(gtab, dtype=torch.int64).reshape(-1).to(dev)
     key = torch.empty(NV, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_dbscan_keys", f"B{B}V{NV}", 0.0, NV * 20.0, lib.pq3d_dbscan_keys, L.ptr(xyzv), L.ptr(offs), L.ptr(gtab),
-                  B, NV, cell, L.ptr(key), st), "pq3d_dbscan_keys")
+    L.call("pq3d_dbscan_keys", xyzv, offs, gtab, B, NV, cell, key, work=(f"B{B}V{NV}", 0.0, NV * 20.0))
     plan = SegmentPlan(key, ndense)
     ncap = min(NV, ndense)
     if Q * ncap >= (1 << 31) - 1 or Q * (NV // 64 + 1) >= (1 << 31):
         raise ValueError(f"use_dbscan: Q * cells ({Q} * {ncap}) must fit 31 bits")
-    wsb = int(lib.pq3d_dbscan_ws_bytes(NV, Q, ncap, B))
+    wsb = int(L.lib().pq3d_dbscan_ws_bytes(NV, Q, ncap, B))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     colseg = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_dbscan_components", f"B{B}V{NV}Q{Q}", 0.0, NV * (Q * 4.0 + 40.0), lib.pq3d_dbscan_components,
-                  L.ptr(masks_in), L.ptr(v2s), L.ptr(offs), L.ptr(qvalid), L.ptr(xyzv), L.ptr(key), L.ptr(gtab), L.ptr(plan.buf),
-                  ndense, B, S, Q, NV, ncap, eps, L.ptr(ws), wsb, L.ptr(colseg), st), "pq3d_dbscan_components")
+    L.call("pq3d_dbscan_components", masks_in, v2s, offs, qvalid, xyzv, key, gtab, plan.buf, ndense, B, S, Q, NV, ncap, eps, ws, wsb,
+           colseg, work=(f"B{B}V{NV}Q{Q}", 0.0, NV * (Q * 4.0 + 40.0)))
     cs = [int(x) for x in colseg.cpu().tolist()]                   # read 2: the columns per scene
     Qp = [cs[b + 1] - cs[b] for b in range(B)]
     Kb = [q if kall else min(K, q * C_) for q in Qp]
@@ -313,28 +296,24 @@ def _dbscan_predictions(logits, masks_in, v2s, v2f, s2f, xyz, xyzv, offs, offs_h
     # D3. columns in (query, smallest voxel) order, their probabilities, top-K over each scene's Q'_b * C candidates
     col = torch.empty(ncol * 4, **i32)
     colprob = torch.empty(ncol * C_, dtype=torch.float32, device=dev)
-    L.check(timed("pq3d_dbscan_columns", f"B{B}N{ncol}C{C_}", 0.0, ncol * C_ * 8.0, lib.pq3d_dbscan_columns, L.ptr(prob),
-                  L.ptr(offs), B, Q, C_, NV, ncap, ncol, L.ptr(ws), L.ptr(col), L.ptr(colprob), st), "pq3d_dbscan_columns")
+    L.call("pq3d_dbscan_columns", prob, offs, B, Q, C_, NV, ncap, ncol, ws, col, colprob, work=(f"B{B}N{ncol}C{C_}", 0.0, ncol * C_ * 8.0))
     seg = colseg * C_
     sel_prob = torch.empty(B, Kmax, dtype=torch.float32, device=dev)
     sel_query, sel_class, kout = torch.empty(B, Kmax, **i32), torch.empty(B, Kmax, **i32), torch.empty(B, **i32)
-    L.check(timed("pq3d_instseg_topk_ragged", f"B{B}N{ncol}C{C_}K{Kmax}", 0.0, ncol * C_ * 4.0 + B * Kmax * 12.0,
-                  lib.pq3d_instseg_topk_ragged, L.ptr(colprob), L.ptr(seg), None, B, C_, Kmax, int(kall), max(Qp) * C_,
-                  L.ptr(sel_prob), L.ptr(sel_query), L.ptr(sel_class), L.ptr(kout), st), "pq3d_instseg_topk_ragged")
+    L.call("pq3d_instseg_topk_ragged", colprob, seg, None, B, C_, Kmax, int(kall), max(Qp) * C_, sel_prob, sel_query, sel_class, kout,
+           work=(f"B{B}N{ncol}C{C_}K{Kmax}", 0.0, ncol * C_ * 4.0 + B * Kmax * 12.0))
     # D4. voxel-level table [B * Vmax, K] + scores, ranked
     Vmax = max(V)
     nch = (Vmax + SEG_CHUNK - 1) // SEG_CHUNK
     table = torch.empty(B * Vmax, Kmax, dtype=torch.float32, device=dev)
     part = torch.empty(B * nch * Kmax * 16, dtype=torch.uint8, device=dev)
-    L.check(timed("pq3d_dbscan_table", f"B{B}V{NV}K{Kmax}", 0.0, NV * (Kmax * 12.0 + 8.0), lib.pq3d_dbscan_table,
-                  L.ptr(masks_in), L.ptr(v2s), L.ptr(offs), L.ptr(ws), L.ptr(col), L.ptr(colseg), L.ptr(sel_query), L.ptr(kout),
-                  B, S, Q, Kmax, NV, ncap, Vmax, L.ptr(table), L.ptr(part), part.numel(), st), "pq3d_dbscan_table")
+    L.call("pq3d_dbscan_table", masks_in, v2s, offs, ws, col, colseg, sel_query, kout, B, S, Q, Kmax, NV, ncap, Vmax, table, part,
+           part.numel(), work=(f"B{B}V{NV}K{Kmax}", 0.0, NV * (Kmax * 12.0 + 8.0)))
     scores = torch.empty(B, Kmax, dtype=torch.float32, device=dev)
     classes = torch.empty(B, Kmax, dtype=torch.int64, device=dev)
     order = torch.empty(B, Kmax, **i32)
-    L.check(timed("pq3d_instseg_rank", f"B{B}K{Kmax}", 0.0, B * nch * Kmax * 16.0, lib.pq3d_instseg_rank, L.ptr(part), nch,
-                  L.ptr(sel_prob), L.ptr(sel_class), B, Kmax, L.ptr(scores), L.ptr(classes), L.ptr(order), st),
-            "pq3d_instseg_rank")
+    L.call("pq3d_instseg_rank", part, nch, sel_prob, sel_class, B, Kmax, scores, classes, order,
+           work=(f"B{B}K{Kmax}", 0.0, B * nch * Kmax * 16.0))
     # D5. vote on voxel-level rows: the table row of point p is b * Vmax + voxel_to_full_maps[p]
     local = torch.cat([torch.arange(v, dtype=torch.int64, device=dev) for v in V])
     return _vote_and_boxes(local, v2f, s2f, xyz, offs, offs_h, table, order, scores, classes, B, Vmax, Sf, Kmax, Kb, P,

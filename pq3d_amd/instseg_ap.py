@@ -39,7 +39,6 @@ import torch
 
 from . import _lib as L
 from .ops import SegmentPlan
-from .profiler import timed
 
 INST = 1000              # PQ3D_AP_INST: id = label * 1000 + instance
 MAX_K = 1024             # PQ3D_AP_MAX_K
@@ -111,7 +110,6 @@ def overlap_tables(masks: Sequence[torch.Tensor], gt_ids: Sequence[torch.Tensor]
     W = (labels.size * INST + 31) // 32
     mbuf = _one_buffer(masks)
     ids = _one_buffer(gt_ids)
-    lib, st = L.lib(), L.stream()
     i32 = dict(dtype=torch.int32, device=dev)
     consts = torch.from_numpy(np.concatenate([rank, labels])).to(dev)
     lab_rank, labs = consts[:rank.size], consts[rank.size:]
@@ -120,8 +118,8 @@ def overlap_tables(masks: Sequence[torch.Tensor], gt_ids: Sequence[torch.Tensor]
     bits = torch.empty(B * W, **i32)
     wpre = torch.empty(B * W, **i32)
     sizes = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_ap_ids", f"B{B}P{NP}", 0.0, NP * 12.0 + B * W * 12.0, lib.pq3d_ap_ids, L.ptr(ids), L.ptr(poff), B, NP,
-                  L.ptr(lab_rank), int(rank.size), W, L.ptr(lkey), L.ptr(bits), L.ptr(wpre), L.ptr(sizes), st), "pq3d_ap_ids")
+    L.call("pq3d_ap_ids", ids, poff, B, NP, lab_rank, int(rank.size), W, lkey, bits, wpre, sizes,
+           work=(f"B{B}P{NP}", 0.0, NP * 12.0 + B * W * 12.0))
     sz = sizes.cpu().numpy()                                # device-to-host read 1: table sizes + error bits
     if sz[B] & 1:
         raise ValueError("overlap_tables: gt_ids holds negative ids")
@@ -135,17 +133,14 @@ def overlap_tables(masks: Sequence[torch.Tensor], gt_ids: Sequence[torch.Tensor]
     offs = torch.from_numpy(np.concatenate([goff_h, toff_h])).to(dev)
     goff, toff = offs[:B + 1], offs[B + 1:]
     key = torch.empty(NP, dtype=torch.int64, device=dev)
-    L.check(timed("pq3d_ap_keys", f"B{B}P{NP}", 0.0, NP * 20.0, lib.pq3d_ap_keys, L.ptr(lkey), L.ptr(bits), L.ptr(wpre),
-                  L.ptr(poff), L.ptr(goff), B, NP, W, L.ptr(key), st), "pq3d_ap_keys")
+    L.call("pq3d_ap_keys", lkey, bits, wpre, poff, goff, B, NP, W, key, work=(f"B{B}P{NP}", 0.0, NP * 20.0))
     plan = SegmentPlan(key, NG)
     out = torch.empty(NG, K, **i32)
-    L.check(timed("pq3d_ap_count", f"B{B}P{NP}K{K}", 0.0, NP * (K + 4.0) + NG * K * 4.0, lib.pq3d_ap_count, L.ptr(mbuf), K,
-                  L.ptr(plan.buf), NP, NG, L.ptr(out), st), "pq3d_ap_count")
+    L.call("pq3d_ap_count", mbuf, K, plan.buf, NP, NG, out, work=(f"B{B}P{NP}K{K}", 0.0, NP * (K + 4.0) + NG * K * 4.0))
     packed = torch.empty(int(toff_h[-1]), **i32)
     max_entries = int((G + K * G + K).max())
-    L.check(timed("pq3d_ap_pack", f"B{B}NG{NG}K{K}", 0.0, NG * K * 4.0 + toff_h[-1] * 4.0, lib.pq3d_ap_pack, L.ptr(out),
-                  L.ptr(plan.buf), NP, NG, L.ptr(bits), L.ptr(wpre), L.ptr(labs), L.ptr(goff), L.ptr(toff), B, K, W,
-                  max_entries, L.ptr(packed), st), "pq3d_ap_pack")
+    L.call("pq3d_ap_pack", out, plan.buf, NP, NG, bits, wpre, labs, goff, toff, B, K, W, max_entries, packed,
+           work=(f"B{B}NG{NG}K{K}", 0.0, NG * K * 4.0 + toff_h[-1] * 4.0))
     host = packed.cpu().numpy()                             # device-to-host read 2: every table of the batch
     res = []
     for b in range(B):
@@ -202,9 +197,8 @@ def gt_boxes(full_masks: Sequence[torch.Tensor], raw_coordinates: Sequence[torch
     ws = torch.empty(max(n_chunks, 1) * BOX_PART_BYTES, dtype=torch.uint8, device=dev)
     boxes = torch.empty(R, 6, dtype=torch.float32, device=dev)
     valid = torch.empty(R, dtype=torch.bool, device=dev)
-    L.check(timed("pq3d_instseg_gt_boxes", f"R{R}P{npts_first}", 0.0, mb + npts_first * 12.0 + R * 25.0,
-                  L.lib().pq3d_instseg_gt_boxes, L.ptr(mbuf), L.ptr(xyz), L.ptr(rinfo), R, n_chunks, L.ptr(ws), ws.numel(),
-                  L.ptr(boxes), L.ptr(valid), L.stream()), "pq3d_instseg_gt_boxes")
+    L.call("pq3d_instseg_gt_boxes", mbuf, xyz, rinfo, R, n_chunks, ws, ws.numel(), boxes, valid,
+           work=(f"R{R}P{npts_first}", 0.0, mb + npts_first * 12.0 + R * 25.0))
     r0 = 0
     for g, _p, _f in rows:
         out.append(dict(boxes=boxes[r0:r0 + g], valid=valid[r0:r0 + g]))

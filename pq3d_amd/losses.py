@@ -14,7 +14,6 @@ layers and scenes, exactly scipy's result): the forward then makes no device-to-
 (``SetCriterion.pad_targets``) decoder + criterion + backward can be captured into one graph."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -88,7 +87,7 @@ def _costs(masks, logits, T, labels, seg_len, n_inst_dev, t_sum, w, ignore_label
     for l in range(n_layers):
         p.X[l] = L.ptr(masks[l])
     p.seg_len, p.sig, p.sp_part, p.sg_part = L.ptr(seg_len), L.ptr(sig), L.ptr(part[0]), L.ptr(part[1])
-    L.check(L.lib().pq3d_mask_cost_prep(C.byref(p), L.stream()), "pq3d_mask_cost_prep")
+    L.call("pq3d_mask_cost_prep", p)
     # ONE grouped + batched exact-f32 MFMA GEMM: groups = (layer, X | sigma(X)), batch = scenes
     TXS = torch.empty(n_layers, 2, B, Nt, Nq, dtype=torch.float32, device=dev)
     Bops = [t for l in range(n_layers) for t in (masks[l], sig[l])]
@@ -103,7 +102,7 @@ def _costs(masks, logits, T, labels, seg_len, n_inst_dev, t_sum, w, ignore_label
     d.seg_len, d.n_inst, d.labels, d.cost = map(L.ptr, (seg_len, n_inst_dev, labels, cost))
     for l in range(n_layers):
         d.cls_logits[l] = L.ptr(logits[l])
-    L.check(L.lib().pq3d_match_cost(C.byref(d), L.stream()), "pq3d_match_cost")
+    L.call("pq3d_match_cost", d)
     return cost, (sig, TXS, part[1].sum(2))
 
 
@@ -160,7 +159,7 @@ class _SetCriterionFn(Function):
         for l in range(n_layers):
             ce.logits[l] = L.ptr(logits[l])
         ce.target, ce.row_loss, ce.lse = L.ptr(tgt), L.ptr(row_loss), L.ptr(lse)
-        L.check(L.lib().pq3d_cross_entropy_fwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_fwd")
+        L.call("pq3d_cross_entropy_fwd", ce)
         cnt = (tgt != crit.ignore_label).sum((1, 2)).clamp(min=1).float()
         losses[:, 0] = row_loss.sum(1) / cnt
         ctx.crit, ctx.n_layers, ctx.keep = crit, n_layers, keep
@@ -205,7 +204,7 @@ class _SetCriterionFn(Function):
         for l in range(n_layers):
             ce.logits[l] = L.ptr(logits[l])
         ce.target, ce.row_loss, ce.lse = L.ptr(tgt), L.ptr(row_loss), L.ptr(lse)
-        L.check(L.lib().pq3d_cross_entropy_fwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_fwd")
+        L.call("pq3d_cross_entropy_fwd", ce)
         cnt = (tgt != crit.ignore_label).sum((1, 2)).clamp(min=1).float()
         losses[:, 0] = torch.where(bad.any(1), nan, row_loss.sum(1) / cnt)
         ctx.crit, ctx.n_layers, ctx.keep = crit, n_layers, keep
@@ -238,13 +237,13 @@ class _SetCriterionFn(Function):
         d.q_idx, d.t_idx, d.n_match, d.g = map(L.ptr, (q_idx_d, t_idx_d, n_match_d, gmd))
         for l in range(n_layers):
             d.dX[l] = L.ptr(dmasks[l])
-        L.check(L.lib().pq3d_matched_mask_grad(C.byref(d), L.stream()), "pq3d_matched_mask_grad")
+        L.call("pq3d_matched_mask_grad", d)
         ce = L.CeDesc()
         ce.layers, ce.C, ce.R, ce.ignore_index = n_layers, dlogits[0].shape[-1], B * Nq, ctx.crit.ignore_label
         for l in range(n_layers):
             ce.logits[l], ce.dlogits[l] = L.ptr(ctx.logits[l]), L.ptr(dlogits[l])
         ce.target, ce.lse, ce.scale = L.ptr(ctx.tgt), L.ptr(ctx.lse), L.ptr(scale)
-        L.check(L.lib().pq3d_cross_entropy_bwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_bwd")
+        L.call("pq3d_cross_entropy_bwd", ce)
         grads = [t.to(dt) for t, dt in zip(dmasks + dlogits, ctx.in_dtypes)]
         return (None,) * 8 + tuple(grads)
 
@@ -380,8 +379,7 @@ class _PaddedMaskLoss(Function):
         B, S, N = X.shape
         nt = (S + 63) // 64
         part = torch.empty(B, nt, N, 4, dtype=torch.float32, device=X.device)
-        L.check(L.lib().pq3d_padded_mask_sums(L.ptr(X), L.ptr(T), L.ptr(P), L.ptr(part), B, S, N, L.stream()),
-                "pq3d_padded_mask_sums")
+        L.call("pq3d_padded_mask_sums", X, T, P, part, B, S, N)
         sums = part.sum(1)                                   # [B, N, 4]
         sb, sp, si, su = sums.unbind(-1)
         valid = sp > 0
@@ -400,8 +398,7 @@ class _PaddedMaskLoss(Function):
         gm = (torch.where(valid, gm_ / (cnt * (sp + 1e-6)), torch.zeros_like(sp))).contiguous()
         gd = (torch.where(valid, gd_ / cnt, torch.zeros_like(sp))).contiguous()
         dX = torch.empty_like(X)
-        L.check(L.lib().pq3d_padded_mask_grad(L.ptr(X), L.ptr(T), L.ptr(P), L.ptr(sums), L.ptr(gm), L.ptr(gd), L.ptr(dX),
-                                              B, S, N, L.stream()), "pq3d_padded_mask_grad")
+        L.call("pq3d_padded_mask_grad", X, T, P, sums, gm, gd, dX, B, S, N)
         return dX, None, None
 
 
@@ -451,9 +448,8 @@ class _RowCE(Function):
         ce = L.CeDesc()
         ce.layers, ce.C, ce.R, ce.ignore_index = 1, Ccls, R, ignore_index
         ce.logits[0], ce.target, ce.row_loss, ce.lse = L.ptr(x), L.ptr(t), L.ptr(row_loss), L.ptr(lse)
-        L.check(L.lib().pq3d_cross_entropy_fwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_fwd")
-        L.check(L.lib().pq3d_cross_entropy_mean(C.byref(ce), L.ptr(loss), L.ptr(inv), L.ptr(add), L.stream()),
-                "pq3d_cross_entropy_mean")
+        L.call("pq3d_cross_entropy_fwd", ce)
+        L.call("pq3d_cross_entropy_mean", ce, loss, inv, add)
         ctx.has_add = add is not None
         ctx.save_for_backward(x, t, lse, inv)
         ctx.ignore_index, ctx.shape, ctx.dtype = ignore_index, logits.shape, logits.dtype
@@ -470,7 +466,7 @@ class _RowCE(Function):
         ce.layers, ce.C, ce.R, ce.ignore_index = 1, x.shape[1], x.shape[0], ctx.ignore_index
         ce.logits[0], ce.dlogits[0], ce.target, ce.lse, ce.scale = L.ptr(x), L.ptr(dl), L.ptr(t), L.ptr(lse), L.ptr(scale)
         ce.scale_mul = L.ptr(inv)
-        L.check(L.lib().pq3d_cross_entropy_bwd(C.byref(ce), L.stream()), "pq3d_cross_entropy_bwd")
+        L.call("pq3d_cross_entropy_bwd", ce)
         dl = dl.view(ctx.shape)
         return (dl if ctx.dtype == torch.float32 else dl.to(ctx.dtype)), None, None, (g if ctx.has_add else None)
 

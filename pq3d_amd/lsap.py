@@ -48,9 +48,7 @@ def linear_sum_assignment_batched(cost: torch.Tensor, n_rows: Optional[torch.Ten
     idx = torch.empty(2, G, M, dtype=torch.int32, device=dev)
     stats = torch.empty(2, G, dtype=torch.int32, device=dev)
     if G:
-        L.check(L.lib().pq3d_lsap_batched(L.ptr(cost), G, R, Cm, cost.stride(1), L.ptr(n_rows), L.ptr(n_cols),
-                                          L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(stats[0]), L.ptr(stats[1]), L.stream()),
-                "pq3d_lsap_batched")
+        L.call("pq3d_lsap_batched", cost, G, R, Cm, cost.stride(1), n_rows, n_cols, idx[0], idx[1], stats[0], stats[1])
     return idx[0], idx[1], stats[0], stats[1]
 
 

@@ -15,7 +15,6 @@ from . import _lib as L
 from . import wgrad
 from .wgrad import dw_long_path, tt_multi, tt_multi_ok  # noqa: F401  (the weight-gradient helpers, importable from ops as before)
 from ._lib import BF16, BF16X3, F32
-from .profiler import timed
 
 _empty = torch.empty
 
@@ -102,7 +101,7 @@ def dropout_mask(rows: int, cols: int, drop: L.Drop) -> torch.Tensor:
     """keep-mask [rows, cols] (bool) of a dropout site -- what the fused kernels draw (tests, debugging)."""
     keep = _empty(rows, cols, dtype=torch.bool, device=drop.seed.device)
     dc = drop.c()
-    L.check(L.lib().pq3d_dropout_mask(L.ptr(keep), rows, cols, C.byref(dc), L.stream()), "pq3d_dropout_mask")
+    L.call("pq3d_dropout_mask", keep, rows, cols, dc)
     return keep
 
 
@@ -111,8 +110,7 @@ def _dropout_apply(x: torch.Tensor, drop: L.Drop, out_dtype=None, alpha: float =
     y = _empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
     cols = x.shape[-1]
     dc = drop.c()
-    L.check(L.lib().pq3d_dropout_apply_scaled(L.ptr(x), L.dt_of(x), L.ptr(y), L.dt_of(y), x.numel() // cols, cols, C.byref(dc),
-                                              float(alpha), L.stream()), "pq3d_dropout_apply")
+    L.call("pq3d_dropout_apply_scaled", x, L.dt_of(x), y, L.dt_of(y), x.numel() // cols, cols, dc, float(alpha))
     return y
 
 
@@ -141,10 +139,8 @@ def split_planes(srcs, adds, his, los) -> None:
     for i in range(0, len(srcs), L.MAXG):
         sl = slice(i, i + L.MAXG)
         n = len(srcs[sl])
-        arr = lambda ts: (C.c_void_p * n)(*[L.ptr(t) for t in ts])
         cnt = (C.c_int64 * n)(*[t.numel() for t in srcs[sl]])
-        L.check(L.lib().pq3d_split_planes(arr(srcs[sl]), arr(adds[sl]), arr(his[sl]), arr(los[sl]), cnt, n, L.stream()),
-                "pq3d_split_planes")
+        L.call("pq3d_split_planes", L.parr(srcs[sl]), L.parr(adds[sl]), L.parr(his[sl]), L.parr(los[sl]), cnt, n)
 
 
 def cast_bf16(ts):
@@ -154,22 +150,20 @@ def cast_bf16(ts):
     assert all(t.numel() == n and t.dtype == torch.float32 and t.is_contiguous() for t in ts) and n % 8 == 0
     for i in range(0, len(ts), L.MAXG):
         k = len(ts[i:i + L.MAXG])
-        arr = lambda xs: (C.c_void_p * k)(*[L.ptr(t) for t in xs])
-        L.check(L.lib().pq3d_add_cast(arr(ts[i:i + k]), arr([None] * k), arr(outs[i:i + k]), k, BF16, n, L.stream()), "pq3d_add_cast")
+        L.call("pq3d_add_cast", L.parr(ts[i:i + k]), L.parr([None] * k), L.parr(outs[i:i + k]), k, BF16, n)
     return outs
 
 
 def colsum(x2d: torch.Tensor) -> torch.Tensor:
     R, N = x2d.shape
     out = _empty(N, dtype=torch.float32, device=x2d.device)
-    L.check(L.lib().pq3d_colsum(L.ptr(x2d), L.dt_of(x2d), R, N, N, L.ptr(out), L.stream()), "pq3d_colsum")
+    L.call("pq3d_colsum", x2d, L.dt_of(x2d), R, N, N, out)
     return out
 
 
 def scale_rows(x: torch.Tensor, rows: int, out_dtype: torch.dtype, scale=None, zero_flag=None, keep_mask=None):
     y = _empty(x.shape, dtype=out_dtype, device=x.device)
-    L.check(L.lib().pq3d_scale_rows(L.ptr(x), L.dt_of(x), L.ptr(y), L.dt_of(y), rows, x.numel() // max(rows, 1),
-                                    L.ptr(scale), L.ptr(zero_flag), L.ptr(keep_mask), L.stream()), "pq3d_scale_rows")
+    L.call("pq3d_scale_rows", x, L.dt_of(x), y, L.dt_of(y), rows, x.numel() // max(rows, 1), scale, zero_flag, keep_mask)
     return y
 
 
@@ -182,17 +176,14 @@ def scale_rows_many(xs, rows: int, out_dtype: torch.dtype, scale=None, zero_flag
     ys = _empty((len(xs),) + tuple(xs[0].shape), dtype=out_dtype, device=xs[0].device)
     for s0 in range(0, len(xs), L.MAXG):
         ch = range(s0, min(s0 + L.MAXG, len(xs)))
-        xa = (C.c_void_p * len(ch))(*[L.ptr(xs[i]) for i in ch])
-        ya = (C.c_void_p * len(ch))(*[L.ptr(ys[i]) for i in ch])
-        L.check(L.lib().pq3d_scale_rows_grouped(xa, ya, len(ch), L.dt_of(ys), rows, C_, L.ptr(scale), L.ptr(zero_flag), L.ptr(keep_mask),
-                                                L.stream()), "pq3d_scale_rows_grouped")
+        L.call("pq3d_scale_rows_grouped", L.parr([xs[i] for i in ch]), L.parr([ys[i] for i in ch]), len(ch), L.dt_of(ys), rows, C_,
+               scale, zero_flag, keep_mask)
     return [ys[i] for i in range(len(xs))]
 
 
 def act_bwd(dy: torch.Tensor, saved: torch.Tensor, act: str, out_dtype: torch.dtype) -> torch.Tensor:
     out = _empty(dy.shape, dtype=out_dtype, device=dy.device)
-    L.check(L.lib().pq3d_act_bwd(L.ptr(dy), L.dt_of(dy), L.ptr(saved), L.dt_of(saved), L.ptr(out), L.dt_of(out),
-                                 L.ACT[act], dy.numel(), L.stream()), "pq3d_act_bwd")
+    L.call("pq3d_act_bwd", dy, L.dt_of(dy), saved, L.dt_of(saved), out, L.dt_of(out), L.ACT[act], dy.numel())
     return out
 
 
@@ -200,8 +191,7 @@ def mask_row_all(mask: torch.Tensor) -> torch.Tensor:
     """[B,Lq,Lk] bool -> [B,Lq] bool, True where the whole row is masked (query_encoder.py:83)."""
     mask = mask.contiguous()
     out = _empty(mask.shape[:-1], dtype=torch.bool, device=mask.device)
-    L.check(L.lib().pq3d_mask_row_all(L.ptr(mask), L.ptr(out), out.numel(), mask.shape[-1], L.stream()),
-            "pq3d_mask_row_all")
+    L.call("pq3d_mask_row_all", mask, out, out.numel(), mask.shape[-1])
     return out
 
 
@@ -212,15 +202,14 @@ def mask_pack(mask: torch.Tensor):
     Lk = mask.shape[-1]
     out = _empty(mask.shape[:-1], dtype=torch.bool, device=mask.device)
     bits = _empty(*mask.shape[:-1], (Lk + 31) // 32, dtype=torch.int32, device=mask.device)
-    L.check(L.lib().pq3d_mask_pack(L.ptr(mask), L.ptr(out), L.ptr(bits), out.numel(), Lk, L.stream()), "pq3d_mask_pack")
+    L.call("pq3d_mask_pack", mask, out, bits, out.numel(), Lk)
     return out, bits
 
 
 def mask_inv_den(masks: Sequence[torch.Tensor]) -> torch.Tensor:
     masks = [m.contiguous() for m in masks]
-    arr = (C.c_void_p * len(masks))(*[L.ptr(m) for m in masks])
     out = _empty(masks[0].shape, dtype=torch.float32, device=masks[0].device)
-    L.check(L.lib().pq3d_mask_inv_den(arr, len(masks), out.numel(), L.ptr(out), L.stream()), "pq3d_mask_inv_den")
+    L.call("pq3d_mask_inv_den", L.parr(masks), len(masks), out.numel(), out)
     return out
 
 
@@ -231,8 +220,7 @@ def pairwise_locs(centers: torch.Tensor, eps: float = 1e-10) -> torch.Tensor:
     if centers.stride(0) != Lq * centers.stride(1):
         centers = centers.contiguous()
     out = _empty(B, Lq, Lq, 5, dtype=torch.float32, device=centers.device)
-    L.check(L.lib().pq3d_pairwise_locs(L.ptr(centers), centers.stride(1), L.ptr(out), B, Lq, eps, L.stream()),
-            "pq3d_pairwise_locs")
+    L.call("pq3d_pairwise_locs", centers, centers.stride(1), out, B, Lq, eps)
     return out
 
 
@@ -245,8 +233,7 @@ def fourier(xyz: torch.Tensor, cmin: torch.Tensor, cmax: torch.Tensor, gauss_B: 
     half = gauss_B.shape[1]
     if out is None:
         out = _empty(B, N, 2 * half, dtype=torch.float32, device=xyz.device)
-    L.check(L.lib().pq3d_fourier(L.ptr(xyz), xyz.stride(1), L.ptr(_c(cmin.float())), L.ptr(_c(cmax.float())),
-                                 L.ptr(_c(gauss_B)), L.ptr(out), B, N, half, L.stream()), "pq3d_fourier")
+    L.call("pq3d_fourier", xyz, xyz.stride(1), _c(cmin.float()), _c(cmax.float()), _c(gauss_B), out, B, N, half)
     return out
 
 
@@ -258,14 +245,9 @@ def fourier_pair(xyz_a: torch.Tensor, xyz_b: torch.Tensor, cmin, cmax, gauss_B) 
     xyz_a, xyz_b = prep(xyz_a), prep(xyz_b)
     B, Na, Nb, half = xyz_a.shape[0], xyz_a.shape[1], xyz_b.shape[1], gauss_B.shape[1]
     out = _empty(B * (Na + Nb), 2 * half, dtype=torch.float32, device=xyz_a.device)
-    L.check(L.lib().pq3d_fourier_pair(L.ptr(xyz_a), xyz_a.stride(1), Na, L.ptr(xyz_b), xyz_b.stride(1), Nb,
-                                      L.ptr(_c(cmin.float())), L.ptr(_c(cmax.float())), L.ptr(_c(gauss_B)), L.ptr(out), B, half,
-                                      L.stream()), "pq3d_fourier_pair")
+    L.call("pq3d_fourier_pair", xyz_a, xyz_a.stride(1), Na, xyz_b, xyz_b.stride(1), Nb, _c(cmin.float()), _c(cmax.float()), _c(gauss_B),
+           out, B, half)
     return out
-
-
-def _parr(ts):
-    return (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
 
 
 def mask_not(masks: Sequence[torch.Tensor]) -> list:
@@ -282,8 +264,7 @@ def mask_not(masks: Sequence[torch.Tensor]) -> list:
     cnt = (C.c_int64 * len(masks))(*[m.numel() for m in masks])
     for s0 in range(0, len(masks), L.MAXG):
         e = min(len(masks), s0 + L.MAXG)
-        L.check(L.lib().pq3d_mask_not(_parr(masks[s0:e]), _parr(outs[s0:e]), C.byref(cnt, 8 * s0), e - s0, L.stream()),
-                "pq3d_mask_not")
+        L.call("pq3d_mask_not", L.parr(masks[s0:e]), L.parr(outs[s0:e]), C.byref(cnt, 8 * s0), e - s0)
     return outs
 
 
@@ -294,7 +275,7 @@ def zero_many(tensors: Sequence[torch.Tensor]) -> None:
         return
     assert all(t.dtype == torch.float32 and t.is_contiguous() for t in ts)
     cnt = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
-    L.check(L.lib().pq3d_zero_many(_parr(ts), cnt, len(ts), L.stream()), "pq3d_zero_many")
+    L.call("pq3d_zero_many", L.parr(ts), cnt, len(ts))
 
 
 def copy_many(dsts: Sequence[torch.Tensor], srcs: Sequence[torch.Tensor]) -> None:
@@ -305,8 +286,7 @@ def copy_many(dsts: Sequence[torch.Tensor], srcs: Sequence[torch.Tensor]) -> Non
     assert all(d_.dtype == torch.float32 and s_.dtype == torch.float32 and d_.is_contiguous() and d_.numel() == s_.numel()
                for d_, s_ in pairs)
     cnt = (C.c_int64 * len(pairs))(*[d_.numel() for d_, _ in pairs])
-    L.check(L.lib().pq3d_copy_many(_parr([s_ for _, s_ in pairs]), _parr([d_ for d_, _ in pairs]), cnt, len(pairs), L.stream()),
-            "pq3d_copy_many")
+    L.call("pq3d_copy_many", L.parr([s_ for _, s_ in pairs]), L.parr([d_ for d_, _ in pairs]), cnt, len(pairs))
 
 
 def sum_n(parts: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -319,7 +299,7 @@ def sum_n(parts: Sequence[torch.Tensor]) -> torch.Tensor:
     for s0 in range(0, len(parts), step):
         chunk = ([out] if out is not None else []) + parts[s0:s0 + step]
         new = torch.empty_like(parts[0])
-        L.check(L.lib().pq3d_sum_n(_parr(chunk), len(chunk), L.ptr(new), new.numel(), L.stream()), "pq3d_sum_n")
+        L.call("pq3d_sum_n", L.parr(chunk), len(chunk), new, new.numel())
         out = new
     return out
 
@@ -333,8 +313,7 @@ def sum_pair(parts_a: Sequence[torch.Tensor], parts_b: Sequence[torch.Tensor]):
     na, nb = parts_a[0].numel(), parts_b[0].numel()
     buf = torch.empty(na + nb, dtype=torch.float32, device=parts_a[0].device)
     oa, ob = buf[:na].view(parts_a[0].shape), buf[na:].view(parts_b[0].shape)
-    L.check(L.lib().pq3d_sum_pair(_parr(parts_a), len(parts_a), L.ptr(oa), na, _parr(parts_b), len(parts_b), L.ptr(ob), nb,
-                                  L.stream()), "pq3d_sum_pair")
+    L.call("pq3d_sum_pair", L.parr(parts_a), len(parts_a), oa, na, L.parr(parts_b), len(parts_b), ob, nb)
     return oa, ob
 
 
@@ -349,7 +328,7 @@ class _MeanAll(Function):
         ws = _MEAN_WS.get(x.device)
         if ws is None:     # arrival counter + per-block partials; the kernel leaves the counter at zero again
             ws = _MEAN_WS[x.device] = torch.zeros(1 + 256, dtype=torch.float32, device=x.device)
-        L.check(L.lib().pq3d_mean_all(L.ptr(x), x.numel(), L.ptr(out), L.ptr(ws), L.stream()), "pq3d_mean_all")
+        L.call("pq3d_mean_all", x, x.numel(), out, ws)
         ctx.shape = x.shape
         return out.view(())
 
@@ -360,7 +339,7 @@ class _MeanAll(Function):
             n *= s_
         dx = _empty(ctx.shape, dtype=torch.float32, device=g.device)
         gg = _c(g.float().reshape(1))
-        L.check(L.lib().pq3d_fill_scaled(L.ptr(dx), n, L.ptr(gg), 1.0 / n, L.stream()), "pq3d_fill_scaled")
+        L.call("pq3d_fill_scaled", dx, n, gg, 1.0 / n)
         return dx
 
 
@@ -376,8 +355,7 @@ class _MeanMany(Function):
         if ws is None:
             ws = _MEAN_WS[key] = torch.zeros(1 + 2 * L.MAXG + 128 * L.MAXG, dtype=torch.float32, device=dev)
         ctx.arr = ((C.c_int64 * n)(*[x.numel() for x in xs]), (C.c_int32 * n)(*modes), (C.c_float * n)(*cmins))
-        L.check(L.lib().pq3d_mean_many(_parr(xs), ctx.arr[0], ctx.arr[1], ctx.arr[2], n, L.ptr(out), L.ptr(ws), L.stream()),
-                "pq3d_mean_many")
+        L.call("pq3d_mean_many", L.parr(xs), ctx.arr[0], ctx.arr[1], ctx.arr[2], n, out, ws)
         ctx.save_for_backward(*xs)
         return out.view(())
 
@@ -386,8 +364,7 @@ class _MeanMany(Function):
         xs = ctx.saved_tensors
         dxs = [torch.empty_like(x) for x in xs]
         gg = _c(g.float().reshape(1))
-        L.check(L.lib().pq3d_mean_many_bwd(_parr(xs), _parr(dxs), ctx.arr[0], ctx.arr[1], ctx.arr[2], len(xs), L.ptr(gg),
-                                           L.stream()), "pq3d_mean_many_bwd")
+        L.call("pq3d_mean_many_bwd", L.parr(xs), L.parr(dxs), ctx.arr[0], ctx.arr[1], ctx.arr[2], len(xs), gg)
         return (None, None, *dxs)
 
 
@@ -713,8 +690,7 @@ class _Attention(Function):
         Lk = k.shape[1]
         fl = 4.0 * B * Lq * Lk * dm
         nb = (q.numel() * 2 + k.numel() * 2) * q.element_size()
-        L.check(timed("pq3d_attn_fwd", f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb, L.lib().pq3d_attn_fwd,
-                      C.byref(d), L.stream()), "pq3d_attn_fwd")
+        L.call("pq3d_attn_fwd", d, work=(f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb))
         ctx.save_for_backward(q, k, v, o, lse, bias, kpm, mask, row_open)
         ctx.cfg = (H, zero_attn, scale, ct)
         ctx.drop = drop
@@ -736,8 +712,7 @@ class _Attention(Function):
         # dQ kernel S, dP, dQ (6) + dK/dV kernel S, dP, dK, dV (8)
         fl = 8.0 * B * Lq * Lk * dm
         nb = (q.numel() * 3 + k.numel() * 4) * q.element_size()
-        L.check(timed("pq3d_attn_bwd", f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb, L.lib().pq3d_attn_bwd,
-                      C.byref(d), L.stream()), "pq3d_attn_bwd")
+        L.call("pq3d_attn_bwd", d, work=(f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb))
         return dq, dk, dv, dbias, None, None, None, None, None, None, None, None
 
 
@@ -780,8 +755,7 @@ class _AddLN(Function):
         d = _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, drop)
         d.sum_branches = int(sum_branches)
         nb = (M + 1 + (x is not None)) * R * dm * 4.0
-        L.check(timed("pq3d_add_ln_fwd", f"R{R}d{dm}M{M}", 0.0, nb, L.lib().pq3d_add_ln_fwd, C.byref(d), L.stream()),
-                "pq3d_add_ln_fwd")
+        L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
         ctx.save_for_backward(x, coef, mean, rstd, *os_, *gammas, *betas)
         ctx.cfg = (eps, rows_per_scene, M, G, bool(sum_branches))
         ctx.drop = drop
@@ -805,8 +779,7 @@ class _AddLN(Function):
             d.d_o[m], d.dgamma[m], d.dbeta[m] = L.ptr(d_os[m]), L.ptr(dgs[m]), L.ptr(dbs[m])
         R, dm = os_[0].numel() // os_[0].shape[-1], os_[0].shape[-1]
         nb = (3 * M + 1 + (x is not None)) * R * dm * 4.0
-        L.check(timed("pq3d_add_ln_bwd", f"R{R}d{dm}M{M}", 0.0, nb, L.lib().pq3d_add_ln_bwd, C.byref(d), L.stream()),
-                "pq3d_add_ln_bwd")
+        L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
         if x is not None and x.dtype != torch.float32:
             dx = dx.to(x.dtype)
         if sum_branches:      # every partial sum receives the gradient of the sum
@@ -876,8 +849,7 @@ class _SpatialBias(Function):
         B, Lq = pl.shape[:2]
         H = W.shape[0]
         bias = _empty(B, H, Lq, Lq, dtype=torch.float32, device=pl.device)
-        L.check(L.lib().pq3d_spatial_bias_fwd(L.ptr(pl), L.ptr(W), L.ptr(bw), L.ptr(bias), B, H, Lq, L.stream()),
-                "pq3d_spatial_bias_fwd")
+        L.call("pq3d_spatial_bias_fwd", pl, W, bw, bias, B, H, Lq)
         ctx.save_for_backward(pl, W, bw)
         return bias
 
@@ -886,8 +858,7 @@ class _SpatialBias(Function):
         pl, W, bw = ctx.saved_tensors
         B, Lq = pl.shape[:2]
         dW, dbw = torch.empty_like(W), torch.empty_like(bw)
-        L.check(L.lib().pq3d_spatial_bias_bwd(L.ptr(pl), L.ptr(W), L.ptr(bw), L.ptr(dbias.contiguous()), L.ptr(dW),
-                                              L.ptr(dbw), B, W.shape[0], Lq, L.stream()), "pq3d_spatial_bias_bwd")
+        L.call("pq3d_spatial_bias_bwd", pl, W, bw, dbias.contiguous(), dW, dbw, B, W.shape[0], Lq)
         return None, dW, dbw
 
 
@@ -902,8 +873,7 @@ class _GateMix(Function):
     def forward(ctx, q, u, g):
         q, u, g = _c(q), _c(u), _c(g)
         y = torch.empty_like(q)
-        L.check(L.lib().pq3d_gate_mix_fwd(L.ptr(q), L.ptr(u), L.ptr(g), L.ptr(y), q.numel(), L.stream()),
-                "pq3d_gate_mix_fwd")
+        L.call("pq3d_gate_mix_fwd", q, u, g, y, q.numel())
         ctx.save_for_backward(q, u, g)
         return y
 
@@ -911,8 +881,7 @@ class _GateMix(Function):
     def backward(ctx, dy):
         q, u, g = ctx.saved_tensors
         dq, du, dg = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        L.check(L.lib().pq3d_gate_mix_bwd(L.ptr(q), L.ptr(u), L.ptr(g), L.ptr(dy.contiguous()), L.ptr(dq), L.ptr(du),
-                                          L.ptr(dg), q.numel(), L.stream()), "pq3d_gate_mix_bwd")
+        L.call("pq3d_gate_mix_bwd", q, u, g, dy.contiguous(), dq, du, dg, q.numel())
         return dq, du, dg
 
 
@@ -927,8 +896,7 @@ class _FillCols(Function):
         x = _c(x)
         y = torch.empty_like(x)
         C_ = x.shape[-1]
-        L.check(L.lib().pq3d_fill_cols(L.ptr(x), L.ptr(y), x.numel() // C_, C_, L.ptr(cols), cols.numel(), value,
-                                       L.stream()), "pq3d_fill_cols")
+        L.call("pq3d_fill_cols", x, y, x.numel() // C_, C_, cols, cols.numel(), value)
         ctx.save_for_backward(cols)
         return y
 
@@ -938,8 +906,7 @@ class _FillCols(Function):
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
         C_ = dy.shape[-1]
-        L.check(L.lib().pq3d_fill_cols(L.ptr(dy), L.ptr(dx), dy.numel() // C_, C_, L.ptr(cols), cols.numel(), 0.0,
-                                       L.stream()), "pq3d_fill_cols")
+        L.call("pq3d_fill_cols", dy, dx, dy.numel() // C_, C_, cols, cols.numel(), 0.0)
         return dx, None, None
 
 
@@ -959,8 +926,7 @@ class SegmentPlan:
         self.index, self.N, self.S = _c(index), int(index.numel()), int(dim_size)
         nbytes = int(L.lib().pq3d_segment_plan_bytes(self.N, self.S))
         self.buf = torch.empty(nbytes, dtype=torch.uint8, device=index.device)
-        L.check(L.lib().pq3d_segment_plan(L.ptr(self.index), self.N, self.S, L.ptr(self.buf), nbytes, L.stream()),
-                "pq3d_segment_plan")
+        L.call("pq3d_segment_plan", self.index, self.N, self.S, self.buf, nbytes)
         self._ws = {}
         self._children = {}
 
@@ -984,10 +950,8 @@ class SegmentPlan:
         # algorithmic bytes: N*C*4 (one row per voxel, as if the up-sampled level were read) + N*8 (ids) +
         # S*C*4 (result)
         nb = self.N * C_ * 4.0 + self.N * 8.0 + self.S * C_ * 4.0
-        L.check(timed("pq3d_segment_reduce", f"N{self.N}S{self.S}C{C_}{'g' if gather is not None else ''}", 0.0, nb,
-                      L.lib().pq3d_segment_reduce, L.ptr(src), src.shape[0], L.ptr(gather), L.ptr(row_div), L.ptr(self.buf),
-                      self.N, self.S, C_, int(mean), L.ptr(out), L.ptr(count), L.ptr(ws), ws.numel(), L.stream()),
-                "pq3d_segment_reduce")
+        L.call("pq3d_segment_reduce", src, src.shape[0], gather, row_div, self.buf, self.N, self.S, C_, int(mean), out, count, ws,
+               ws.numel(), work=(f"N{self.N}S{self.S}C{C_}{'g' if gather is not None else ''}", 0.0, nb))
         return out, count
 
 
@@ -999,9 +963,7 @@ def segment_gather(table: torch.Tensor, index: torch.Tensor, count: Optional[tor
     table, index = _c(table), _c(index)
     out = _empty(index.numel(), table.shape[1], dtype=torch.float32, device=table.device)
     N, S, C_ = index.numel(), table.shape[0], table.shape[1]
-    L.check(timed("pq3d_segment_gather", f"N{N}S{S}C{C_}", 0.0, N * C_ * 4.0 + N * 8.0 + S * C_ * 4.0,
-                  L.lib().pq3d_segment_gather, L.ptr(table), L.ptr(index), L.ptr(count), L.ptr(out), N, S, C_, L.stream()),
-            "pq3d_segment_gather")
+    L.call("pq3d_segment_gather", table, index, count, out, N, S, C_, work=(f"N{N}S{S}C{C_}", 0.0, N * C_ * 4.0 + N * 8.0 + S * C_ * 4.0))
     return out
 
 
@@ -1113,8 +1075,7 @@ class _LinearLNGroup(Function):
         d.dt_y = F32
         for g in range(G):
             d.ys[g] = L.ptr(ys[g])
-        L.check(timed("pq3d_add_ln_fwd", f"R{R}d{N}M{G}i", 0.0, 2.0 * G * R * N * 4, L.lib().pq3d_add_ln_fwd, C.byref(d),
-                      L.stream()), "pq3d_add_ln_fwd")
+        L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 2.0 * G * R * N * 4))
         ctx.save_for_backward(lin, mean, rstd, *xs, *Ws, *gam, *bet)
         ctx.cfg = (ct, eps, G, need_dx)
         ctx.pptr = [a.data_ptr() for a in (*Ws, *bs, *gam, *bet)]   # order of the returned parameter gradients
@@ -1153,8 +1114,7 @@ class _LinearLNGroup(Function):
         d.accumulate = 1
         for g in range(G):
             d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dlin[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
-        L.check(timed("pq3d_add_ln_bwd", f"R{R}d{N}M{G}i", 0.0, 3.0 * G * R * N * 4, L.lib().pq3d_add_ln_bwd, C.byref(d),
-                      L.stream()), "pq3d_add_ln_bwd")
+        L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 3.0 * G * R * N * 4))
         probs = [(dlin[g], xs[g], None, dWs[g], dbl[g]) for g in range(G)]
         if fuse and wgrad.tt_multi_fits(probs, N, K, R, ct):
             # short reductions only: the encoders of small batches / short memories -- one launch with the fused bias gradient,
@@ -1403,7 +1363,7 @@ class _RMSNorm(Function):
         R = x.numel() // d_
         y = torch.empty_like(x)
         rstd = _empty(R, dtype=torch.float32, device=x.device)
-        L.check(L.lib().pq3d_rmsnorm_fwd(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(rstd), R, d_, eps, L.stream()), "pq3d_rmsnorm_fwd")
+        L.call("pq3d_rmsnorm_fwd", x, w, y, rstd, R, d_, eps)
         ctx.save_for_backward(x, w, rstd)
         ctx.pptr = w.data_ptr()
         return (y, x.view_as(x)) if res else y
@@ -1423,10 +1383,8 @@ class _RMSNorm(Function):
         dxm, dc = None, None
         if gd is not None and gd[0] is not None and gd[0].p > 0.0:
             dxm, dc = torch.empty_like(x), gd[0].c()
-        L.check(L.lib().pq3d_rmsnorm_bwd_res_drop(L.ptr(x), L.ptr(w), L.ptr(rstd), L.ptr(dy), L.ptr(dres), L.ptr(dx), L.ptr(dw),
-                                                  x.numel() // d_, d_, 1 if slot is not None else 0,
-                                                  C.byref(dc) if dc is not None else None, L.ptr(dxm), L.stream()),
-                "pq3d_rmsnorm_bwd_res_drop")
+        L.call("pq3d_rmsnorm_bwd_res_drop", x, w, rstd, dy, dres, dx, dw, x.numel() // d_, d_, 1 if slot is not None else 0,
+               dc, dxm)
         if dxm is not None:
             gd[1]["g"], gd[1]["of"] = dxm, dx
         return dx, (dw if (slot is None or give) else None), None, None, None
@@ -1451,11 +1409,9 @@ class _Embedding(Function):
         out = _empty(*ids.shape, d_, dtype=torch.float32, device=table.device)
         if drop is not None:
             dc = drop.c()
-            L.check(L.lib().pq3d_embedding_drop_fwd(L.ptr(table), L.ptr(ids), L.ptr(out), ids.numel(), d_, C.byref(dc), L.stream()),
-                    "pq3d_embedding_drop_fwd")
+            L.call("pq3d_embedding_drop_fwd", table, ids, out, ids.numel(), d_, dc)
         else:
-            L.check(L.lib().pq3d_embedding_fwd(L.ptr(table), L.ptr(ids), L.ptr(out), ids.numel(), d_, L.stream()),
-                    "pq3d_embedding_fwd")
+            L.call("pq3d_embedding_fwd", table, ids, out, ids.numel(), d_)
         ctx.save_for_backward(ids)
         ctx.shape, ctx.drop = table.shape, drop
         ctx.pptr = table.data_ptr()
@@ -1469,11 +1425,9 @@ class _Embedding(Function):
         dout = dout.contiguous().float()
         if ctx.drop is not None:
             dc = ctx.drop.c()
-            L.check(L.lib().pq3d_embedding_drop_bwd_acc(L.ptr(dout), L.ptr(ids), L.ptr(dt), ids.numel(), ctx.shape[1], C.byref(dc),
-                                                        L.stream()), "pq3d_embedding_drop_bwd_acc")
+            L.call("pq3d_embedding_drop_bwd_acc", dout, ids, dt, ids.numel(), ctx.shape[1], dc)
         else:
-            L.check(L.lib().pq3d_embedding_bwd_acc(L.ptr(dout), L.ptr(ids), L.ptr(dt), ids.numel(), ctx.shape[1], L.stream()),
-                    "pq3d_embedding_bwd_acc")
+            L.call("pq3d_embedding_bwd_acc", dout, ids, dt, ids.numel(), ctx.shape[1])
         return (dt if (slot is None or give) else None), None, None
 
 
@@ -1495,8 +1449,7 @@ class _T5Prep(Function):
             assert ev.dtype == torch.bool and ev.shape[0] == B
             N = ev.shape[1]
             kpm = _empty(B, N, dtype=torch.bool, device=dev)
-        L.check(L.lib().pq3d_t5_prep(L.ptr(labels), int(start_id), int(pad_id), L.ptr(rel), L.ptr(buckets), L.ptr(ev), L.ptr(ids),
-                                     L.ptr(bias), L.ptr(kpm), B, T, H, N, L.stream()), "pq3d_t5_prep")
+        L.call("pq3d_t5_prep", labels, int(start_id), int(pad_id), rel, buckets, ev, ids, bias, kpm, B, T, H, N)
         ctx.save_for_backward(buckets)
         ctx.cfg = (B, T, H, rel.shape[0])
         ctx.pptr = rel.data_ptr()
@@ -1515,8 +1468,7 @@ class _T5Prep(Function):
         slot, give = arena_take([ctx.pptr], [NB * H])
         drel = slot[0].view(NB, H) if slot is not None else _empty(NB, H, dtype=torch.float32, device=dbias.device)
         dbias = dbias.contiguous().float()
-        L.check(L.lib().pq3d_t5_bias_bwd(L.ptr(dbias), L.ptr(buckets), L.ptr(drel), B, T, H, NB, 1 if slot is not None else 0,
-                                         L.stream()), "pq3d_t5_bias_bwd")
+        L.call("pq3d_t5_bias_bwd", dbias, buckets, drel, B, T, H, NB, 1 if slot is not None else 0)
         return (drel if (slot is None or give) else None), None, None, None, None, None, None
 
 
@@ -1579,6 +1531,28 @@ def _chain_ws(dev) -> torch.Tensor:
     return w
 
 
+def _chain_err(dev) -> torch.Tensor:
+    """Error word of the chains on a device: set by a hand-off that gave up, polled by chain_check."""
+    err = _CHAIN_ERR.get(dev)
+    if err is None:
+        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return err
+
+
+def _chain_set(c, any_dtype=(), /, **fields) -> None:
+    """c.<name> = pointer of each tensor, asserted contiguous and fp32 (the names in any_dtype: contiguous only)."""
+    for n, t in fields.items():
+        assert t.is_contiguous() and (n in any_dtype or t.dtype == torch.float32), n
+        setattr(c, n, L.ptr(t))
+
+
+def _chain_set_m(c, m: int, any_dtype=(), /, **fields) -> None:
+    """c.<name>[m] = pointer of each tensor (the per-memory / per-projection pointer arrays), asserted as in _chain_set."""
+    for n, t in fields.items():
+        assert t.is_contiguous() and (n in any_dtype or t.dtype == torch.float32), n
+        getattr(c, n)[m] = L.ptr(t)
+
+
 def chain_ffn_ok(R: int, d: int, F_: int) -> bool:
     return d == 256 and F_ == 2048 and 1 <= R <= 2048
 
@@ -1601,16 +1575,10 @@ def chain_ffn_fwd(o_s, Wo, bo, x1s, g1, be1, eps1, W1, b1, W2, b2, g2, be2, eps2
     f, x2, x3, z = e(o_s.shape), e(o_s.shape), e(o_s.shape), e(o_s.shape)
     h, zp = e(*o_s.shape[:-1], F_), e(4, *o_s.shape)
     mean1, rstd1, mean2, rstd2 = e(1, R), e(1, R), e(1, R), e(1, R)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainFfnDesc()
     c.R, c.d, c.F, c.eps1, c.eps2 = R, d, F_, eps1, eps2
-    for n, t in (("o_s", o_s), ("Wo", Wo), ("bo", bo), ("x1s", x1s), ("g1", g1), ("be1", be1), ("f", f), ("x2", x2), ("mean1", mean1),
-                 ("rstd1", rstd1), ("W1", W1), ("b1", b1), ("h", h), ("W2", W2), ("b2", b2), ("zp", zp), ("z", z), ("g2", g2),
-                 ("be2", be2), ("x3", x3), ("mean2", mean2), ("rstd2", rstd2), ("flags", flags), ("err", err)):
-        assert t.is_contiguous() and (n in ("flags", "err") or t.dtype == torch.float32), n
-        setattr(c, n, L.ptr(t))
+    _chain_set(c, ("flags", "err"), o_s=o_s, Wo=Wo, bo=bo, x1s=x1s, g1=g1, be1=be1, f=f, x2=x2, mean1=mean1, rstd1=rstd1, W1=W1, b1=b1, h=h,
+               W2=W2, b2=b2, zp=zp, z=z, g2=g2, be2=be2, x3=x3, mean2=mean2, rstd2=rstd2, flags=flags, err=_chain_err(dev))
     if sa is not None:
         q_, k_, v_, bias_, kpm_, lse_, scale_ = sa
         Nq = q_.shape[-2]
@@ -1631,15 +1599,13 @@ def chain_ffn_fwd(o_s, Wo, bo, x1s, g1, be1, eps1, W1, b1, W2, b2, g2, be2, eps2
         assert qpos.is_contiguous() and qpos.dtype == torch.float32 and len(Wqs) <= 3
         c.nq, c.qpos, c.qout_f32 = len(Wqs), L.ptr(qpos), int(q_dtype == torch.float32)
         for m, (w_, b_) in enumerate(zip(Wqs, bqs)):
-            assert w_.is_contiguous() and b_.is_contiguous() and w_.dtype == torch.float32
-            c.Wq[m], c.bq[m], c.qout[m] = L.ptr(w_), L.ptr(b_), L.ptr(qn[m])
-    from .profiler import timed
+            _chain_set_m(c, m, ("bq", "qout"), Wq=w_, bq=b_, qout=qn[m])
     fl = 2.0 * R * d * (d + 2 * F_)
     nb = 4.0 * (R * d * 9 + 2 * R * F_ + d * d + 2 * d * F_)
     if sa is not None:   # the self-attention core of step 0: scores + value contraction, q / k / v in, bias in
         fl += 4.0 * R * sa[0].shape[-2] * d
         nb += 4.0 * (3 * R * d + (sa[3].numel() if sa[3] is not None else 0))
-    L.check(timed("pq3d_chain_ffn_fwd", f"R{R}d{d}F{F_}", fl, nb, L.lib().pq3d_chain_ffn_fwd, C.byref(c), L.stream()), "pq3d_chain_ffn_fwd")
+    L.call("pq3d_chain_ffn_fwd", c, work=(f"R{R}d{d}F{F_}", fl, nb))
     return (f, x2, mean1, rstd1, h, zp, z, x3, mean2, rstd2) + ((qn,) if qn is not None else ())
 
 
@@ -1656,28 +1622,20 @@ def chain_ca_fwd(o_all, Wos, bos, x, gammas, betas, eps, coef, rows_per_scene, q
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     op_all, x1, qkv = e(M, *x.shape), e(x.shape), e(3, *x.shape)
     mean, rstd = e(M, R), e(M, R)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainCaDesc()
     c.R, c.d, c.M, c.rows_per_scene, c.eps = R, d, M, rows_per_scene, eps
-    assert o_all.dtype in (torch.bfloat16, torch.float32) and o_all.is_contiguous() and x.is_contiguous() and qpos.is_contiguous()
+    assert o_all.dtype in (torch.bfloat16, torch.float32) and o_all.is_contiguous()
     c.o_f32 = int(o_all.dtype == torch.float32)
-    assert x.dtype == torch.float32 and qpos.dtype == torch.float32
     for m in range(M):
-        for n, t in (("o", o_all[m]), ("Wo", Wos[m]), ("bo", bos[m]), ("gamma", gammas[m]), ("beta", betas[m]), ("op", op_all[m])):
-            assert t.is_contiguous() and (n == "o" or t.dtype == torch.float32), n
-            getattr(c, n)[m] = L.ptr(t)
+        _chain_set_m(c, m, ("o",), o=o_all[m], Wo=Wos[m], bo=bos[m], gamma=gammas[m], beta=betas[m], op=op_all[m])
     for g in range(3):
-        for n, t in (("Wqkv", Wqkv[g]), ("bqkv", bqkv[g]), ("qkv", qkv[g])):
-            assert t.is_contiguous() and t.dtype == torch.float32, n
-            getattr(c, n)[g] = L.ptr(t)
+        _chain_set_m(c, g, Wqkv=Wqkv[g], bqkv=bqkv[g], qkv=qkv[g])
+    _chain_set(c, ("flags", "err"), x=x, x1=x1, mean=mean, rstd=rstd, qpos=qpos, flags=flags, err=_chain_err(dev))
     if coef is not None:
-        assert coef.is_contiguous() and coef.dtype == torch.float32
-    c.x, c.coef, c.x1, c.mean, c.rstd, c.qpos, c.flags, c.err = map(L.ptr, (x, coef, x1, mean, rstd, qpos, flags, err))
+        _chain_set(c, coef=coef)
     fl = 2.0 * R * d * d * (M + 3)
     nb = 4.0 * (R * d * (2 * M + 6) + (M + 3) * d * d) + 2.0 * M * R * d
-    L.check(timed("pq3d_chain_ca_fwd", f"R{R}d{d}M{M}", fl, nb, L.lib().pq3d_chain_ca_fwd, C.byref(c), L.stream()), "pq3d_chain_ca_fwd")
+    L.call("pq3d_chain_ca_fwd", c, work=(f"R{R}d{d}M{M}", fl, nb))
     return op_all, x1, mean, rstd, qkv
 
 
@@ -1694,23 +1652,17 @@ def chain_mh_fwd(x, W0, b0, gamma, beta, eps, W4, b4, colfill, fill, Wqs, bqs, f
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     h1, h2, cls, qm = e(x.shape), e(x.shape), e(*x.shape[:-1], C_), e(Mm, *x.shape)
     mean, rstd = e(1, R), e(1, R)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainMhDesc()
     c.R, c.d, c.Mm, c.C, c.eps, c.fill = R, d, Mm, C_, eps, fill
-    for n, t in (("x", x), ("W0", W0), ("b0", b0), ("gamma", gamma), ("beta", beta), ("W4", W4), ("b4", b4)):
-        assert t.is_contiguous() and t.dtype == torch.float32, n
+    _chain_set(c, ("flags", "err"), x=x, W0=W0, b0=b0, gamma=gamma, beta=beta, W4=W4, b4=b4, h1=h1, h2=h2, mean=mean, rstd=rstd, cls=cls,
+               flags=flags, err=_chain_err(dev))
     assert colfill is None or (colfill.dtype == torch.int32 and colfill.numel() == C_ and colfill.is_contiguous())
+    c.colfill = L.ptr(colfill)
     for m in range(Mm):
-        for n, t in (("Wq", Wqs[m]), ("bq", bqs[m]), ("qm", qm[m])):
-            assert t.is_contiguous() and t.dtype == torch.float32, n
-            getattr(c, n)[m] = L.ptr(t)
-    c.x, c.W0, c.b0, c.gamma, c.beta, c.W4, c.b4, c.colfill = map(L.ptr, (x, W0, b0, gamma, beta, W4, b4, colfill))
-    c.h1, c.h2, c.mean, c.rstd, c.cls, c.flags, c.err = map(L.ptr, (h1, h2, mean, rstd, cls, flags, err))
+        _chain_set_m(c, m, Wq=Wqs[m], bq=bqs[m], qm=qm[m])
     fl = 2.0 * R * d * (d * (1 + Mm) + C_)
     nb = 4.0 * (R * d * (3 + Mm) + R * C_ + (1 + Mm) * d * d + C_ * d)
-    L.check(timed("pq3d_chain_mh_fwd", f"R{R}d{d}M{Mm}C{C_}", fl, nb, L.lib().pq3d_chain_mh_fwd, C.byref(c), L.stream()), "pq3d_chain_mh_fwd")
+    L.call("pq3d_chain_mh_fwd", c, work=(f"R{R}d{d}M{Mm}C{C_}", fl, nb))
     return h1, h2, mean, rstd, cls, qm
 
 
@@ -1727,9 +1679,6 @@ def chain_mh_bwd(dc, colfill, W4, h1, mean, rstd, gamma, dgamma, dbeta, W0, cur,
     assert dcl is None or (dcl.is_contiguous() and dcl.dtype == torch.float32 and dcl.shape == dc.shape)
     dh2, out = torch.empty_like(h1), torch.empty_like(h1)
     dpre = torch.empty(h1.shape, dtype=torch.bfloat16, device=dev)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainMhBwdDesc()
     c.R, c.d, c.Mm, c.C = R, d, Mm, C_
     c.dq_f32 = int(Mm > 0 and dqs[0].dtype == torch.float32)
@@ -1738,26 +1687,20 @@ def chain_mh_bwd(dc, colfill, W4, h1, mean, rstd, gamma, dgamma, dbeta, W0, cur,
         assert cur is None and dq_all.dtype == torch.bfloat16 and dq_all.is_contiguous() and 1 <= dq_all.shape[0] <= 3
         c.nq = dq_all.shape[0]
         for m in range(c.nq):
-            assert Wqc[m].is_contiguous() and Wqc[m].dtype == torch.float32
-            c.dqc[m], c.Wqc[m] = L.ptr(dq_all[m]), L.ptr(Wqc[m])
-        cur = dxr
-        c.dxr, c.gq = L.ptr(dxr), L.ptr(gq)
-        assert gq.is_contiguous() and gq.dtype == torch.float32
-    for n, t in (("dc", dc), ("W4", W4), ("h1", h1), ("mean", mean), ("rstd", rstd), ("gamma", gamma), ("dgamma", dgamma),
-                 ("dbeta", dbeta), ("W0", W0), ("cur", cur)):
-        assert t.is_contiguous() and t.dtype == torch.float32, n
+            _chain_set_m(c, m, ("dqc",), dqc=dq_all[m], Wqc=Wqc[m])
+        _chain_set(c, dxr=dxr, gq=gq)     # (dxr stands in for cur; c.cur stays NULL)
+    else:
+        _chain_set(c, cur=cur)
+    _chain_set(c, ("dpre", "flags", "err"), dc=dc, W4=W4, h1=h1, mean=mean, rstd=rstd, gamma=gamma, dgamma=dgamma, dbeta=dbeta, W0=W0,
+               dh2=dh2, dpre=dpre, out=out, flags=flags, err=_chain_err(dev), lnws=_chain_ws(dev))
     assert colfill is None or (colfill.dtype == torch.int32 and colfill.numel() == C_ and colfill.is_contiguous())
+    c.colfill, c.dcl = L.ptr(colfill), L.ptr(dcl)
     for m in range(Mm):
-        assert dqs[m].is_contiguous() and dqs[m].dtype == dqs[0].dtype and dqs[m].dtype in (torch.float32, torch.bfloat16)
-        assert Wqs[m].is_contiguous() and Wqs[m].dtype == torch.float32
-        c.dq[m], c.Wq[m] = L.ptr(dqs[m]), L.ptr(Wqs[m])
-    c.dc, c.colfill, c.dcl, c.W4, c.h1, c.mean, c.rstd, c.gamma, c.dgamma, c.dbeta = map(
-        L.ptr, (dc, colfill, dcl, W4, h1, mean, rstd, gamma, dgamma, dbeta))
-    c.dh2, c.dpre, c.W0, c.cur, c.out, c.flags, c.err, c.lnws = map(
-        L.ptr, (dh2, dpre, W0, cur if prev is None else None, out, flags, err, _chain_ws(dev)))
+        assert dqs[m].dtype == dqs[0].dtype and dqs[m].dtype in (torch.float32, torch.bfloat16)
+        _chain_set_m(c, m, ("dq",), dq=dqs[m], Wq=Wqs[m])
     fl = 2.0 * R * d * (C_ + d * (1 + Mm))
     nb = 4.0 * (R * C_ * 2 + R * d * (5 + Mm) + C_ * d + (1 + Mm) * d * d) + 2.0 * R * d
-    L.check(timed("pq3d_chain_mh_bwd", f"R{R}d{d}M{Mm}C{C_}", fl, nb, L.lib().pq3d_chain_mh_bwd, C.byref(c), L.stream()), "pq3d_chain_mh_bwd")
+    L.call("pq3d_chain_mh_bwd", c, work=(f"R{R}d{d}M{Mm}C{C_}", fl, nb))
     return (dcl if dcl is not None else dc), dpre, out
 
 
@@ -1779,25 +1722,20 @@ def chain_ffn_bwd(dx, x2, z, g2, mean2, rstd2, dg2, db2, W2, h, W1, x1s, f, g1, 
         dxo = torch.empty_like(like)
         dx = dxo   # (pointer only: not read by the kernel)
     part = torch.empty(4, R, d, dtype=torch.float32, device=dev)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainFfnBwdDesc()
     c.R, c.d, c.F = R, d, F_
-    for n, t in (("dx", dx), ("x2", x2), ("z", z), ("g2", g2), ("mean2", mean2), ("rstd2", rstd2), ("dg2", dg2), ("db2", db2), ("dy", dy),
-                 ("W2", W2), ("h", h), ("dhp", dhp), ("W1", W1), ("part", part), ("x1s", x1s), ("f", f), ("g1", g1), ("mean1", mean1),
-                 ("rstd1", rstd1), ("dg1", dg1), ("db1", db1), ("df", df), ("flags", flags), ("err", err), ("lnws", _chain_ws(dev))):
-        assert t.is_contiguous() and (n in ("flags", "err", "dhp") or t.dtype == torch.float32), n
-        setattr(c, n, L.ptr(t))
+    _chain_set(c, ("flags", "err", "dhp"), dx=dx, x2=x2, z=z, g2=g2, mean2=mean2, rstd2=rstd2, dg2=dg2, db2=db2, dy=dy, W2=W2, h=h, dhp=dhp,
+               W1=W1, part=part, x1s=x1s, f=f, g1=g1, mean1=mean1, rstd1=rstd1, dg1=dg1, db1=db1, df=df, flags=flags, err=_chain_err(dev),
+               lnws=_chain_ws(dev))
     if prev is not None:
-        assert dq_all.dtype == torch.bfloat16 and dq_all.is_contiguous() and dxr.is_contiguous() and gq.is_contiguous() and len(Wqs) <= 3
-        c.nq, c.dxr, c.gq, c.dxo = len(Wqs), L.ptr(dxr), L.ptr(gq), L.ptr(dxo)
+        assert dq_all.dtype == torch.bfloat16 and dq_all.is_contiguous() and len(Wqs) <= 3
+        c.nq = len(Wqs)
+        _chain_set(c, ("dxr", "gq", "dxo"), dxr=dxr, gq=gq, dxo=dxo)
         for m, w_ in enumerate(Wqs):
-            assert w_.is_contiguous() and w_.dtype == torch.float32
-            c.dq[m], c.Wq[m] = L.ptr(dq_all[m]), L.ptr(w_)
+            _chain_set_m(c, m, ("dq",), dq=dq_all[m], Wq=w_)
     fl = 2.0 * R * d * 2 * F_
     nb = 4.0 * (R * d * 12 + R * F_ + 2 * d * F_) + 2.0 * 2 * R * F_
-    L.check(timed("pq3d_chain_ffn_bwd", f"R{R}d{d}F{F_}", fl, nb, L.lib().pq3d_chain_ffn_bwd, C.byref(c), L.stream()), "pq3d_chain_ffn_bwd")
+    L.call("pq3d_chain_ffn_bwd", c, work=(f"R{R}d{d}F{F_}", fl, nb))
     return (dy, dhp, df) if prev is None else (dy, dhp, df, dxo)
 
 
@@ -1810,29 +1748,19 @@ def chain_sa_bwd(dqkv, Wl, aux2, x, op_all, gammas, mean, rstd, coef, rows_per_s
     dop = torch.empty(M, *x.shape, dtype=torch.float32, device=dev)
     dxr = torch.empty(x.shape, dtype=torch.float32, device=dev)
     do_all = torch.empty(M, *x.shape, dtype=torch.bfloat16, device=dev)
-    err = _CHAIN_ERR.get(dev)
-    if err is None:
-        err = _CHAIN_ERR[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     c = L.ChainSaBwdDesc()
     c.R, c.d, c.M, c.rows_per_scene = R, d, M, rows_per_scene
     for g in range(3):
-        for n, t in (("dqkv", dqkv[g]), ("Wl", Wl[g]), ("g3", g3[g])):
-            assert t.is_contiguous() and t.dtype == torch.float32, n
-            getattr(c, n)[g] = L.ptr(t)
+        _chain_set_m(c, g, dqkv=dqkv[g], Wl=Wl[g], g3=g3[g])
     for m in range(M):
-        for n, t in (("op", op_all[m]), ("gamma", gammas[m]), ("dop", dop[m]), ("dgamma", dgammas[m]), ("dbeta", dbetas[m]), ("Wo", Wos[m]),
-                     ("do_all", do_all[m])):
-            assert t.is_contiguous() and (n == "do_all" or t.dtype == torch.float32), n
-            getattr(c, n)[m] = L.ptr(t)
-    for t in (aux2, x, mean, rstd):
-        assert t.is_contiguous() and t.dtype == torch.float32
+        _chain_set_m(c, m, ("do_all",), op=op_all[m], gamma=gammas[m], dop=dop[m], dgamma=dgammas[m], dbeta=dbetas[m], Wo=Wos[m],
+                     do_all=do_all[m])
+    _chain_set(c, ("flags", "err"), aux2=aux2, x=x, mean=mean, rstd=rstd, dxr=dxr, flags=flags, err=_chain_err(dev), lnws=_chain_ws(dev))
     if coef is not None:
-        assert coef.is_contiguous() and coef.dtype == torch.float32
-    c.aux2, c.x, c.mean, c.rstd, c.coef, c.dxr, c.flags, c.err = map(L.ptr, (aux2, x, mean, rstd, coef, dxr, flags, err))
-    c.lnws = L.ptr(_chain_ws(dev))
+        _chain_set(c, coef=coef)
     fl = 2.0 * R * d * d * (3 + M)
     nb = 4.0 * (R * d * (8 + 3 * M) + (3 + M) * d * d) + 2.0 * M * R * d
-    L.check(timed("pq3d_chain_sa_bwd", f"R{R}d{d}M{M}", fl, nb, L.lib().pq3d_chain_sa_bwd, C.byref(c), L.stream()), "pq3d_chain_sa_bwd")
+    L.call("pq3d_chain_sa_bwd", c, work=(f"R{R}d{d}M{M}", fl, nb))
     return g3, dop, dxr, do_all
 
 

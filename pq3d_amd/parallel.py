@@ -74,11 +74,9 @@ class NativeComm:
             sc = self._scratch.get(t.data_ptr())
             if sc is None or sc.numel() < need:     # fixed address per bucket: capturable
                 sc = self._scratch[t.data_ptr()] = torch.empty(need, dtype=torch.uint8, device=t.device)
-            _lib.check(L.pq3d_allreduce_grads_wire(self._h, t.data_ptr(), t.numel(), sc.data_ptr(), sc.numel(), int(mean), _lib.stream()),
-                       "pq3d_allreduce_grads_wire")
+            _lib.call("pq3d_allreduce_grads_wire", self._h, t, t.numel(), sc, sc.numel(), int(mean))
         else:
-            _lib.check(L.pq3d_allreduce_grads(self._h, t.data_ptr(), t.numel(), _lib.dt_of(t), int(mean), _lib.stream()),
-                       "pq3d_allreduce_grads")
+            _lib.call("pq3d_allreduce_grads", self._h, t, t.numel(), _lib.dt_of(t), int(mean))
 
     def close(self) -> None:
         if self._h:

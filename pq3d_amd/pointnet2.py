@@ -22,8 +22,7 @@ class FurthestPointSampling(Function):
         xyz = _f(xyz)
         B, N, _ = xyz.shape
         idx = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
-        L.check(L.lib().pq3d_furthest_point_sampling(L.ptr(xyz), L.ptr(idx), B, N, npoint, L.stream()),
-                "pq3d_furthest_point_sampling")
+        L.call("pq3d_furthest_point_sampling", xyz, idx, B, N, npoint)
         ctx.mark_non_differentiable(idx)
         return idx
 
@@ -43,8 +42,7 @@ class GatherOperation(Function):
         features, idx = _f(features), idx.contiguous().int()
         B, C, N = features.shape
         out = torch.empty(B, C, idx.shape[1], dtype=torch.float32, device=features.device)
-        L.check(L.lib().pq3d_gather_points(L.ptr(features), L.ptr(idx), L.ptr(out), B, C, N, idx.shape[1], L.stream()),
-                "pq3d_gather_points")
+        L.call("pq3d_gather_points", features, idx, out, B, C, N, idx.shape[1])
         ctx.for_backwards = (idx, C, N)
         return out
 
@@ -54,8 +52,7 @@ class GatherOperation(Function):
         g = _f(grad_out)
         B = g.shape[0]
         gf = torch.empty(B, C, N, dtype=torch.float32, device=g.device)
-        L.check(L.lib().pq3d_gather_points_grad(L.ptr(g), L.ptr(idx), L.ptr(gf), B, C, N, idx.shape[1], L.stream()),
-                "pq3d_gather_points_grad")
+        L.call("pq3d_gather_points_grad", g, idx, gf, B, C, N, idx.shape[1])
         return gf, None
 
 
@@ -71,8 +68,7 @@ class ThreeNN(Function):
         B, n, _ = unknown.shape
         d2 = torch.empty(B, n, 3, dtype=torch.float32, device=unknown.device)
         idx = torch.empty(B, n, 3, dtype=torch.int32, device=unknown.device)
-        L.check(L.lib().pq3d_three_nn(L.ptr(unknown), L.ptr(known), L.ptr(d2), L.ptr(idx), B, n, known.shape[1], L.stream()),
-                "pq3d_three_nn")
+        L.call("pq3d_three_nn", unknown, known, d2, idx, B, n, known.shape[1])
         ctx.mark_non_differentiable(idx)
         return torch.sqrt(d2), idx
 
@@ -93,8 +89,7 @@ class ThreeInterpolate(Function):
         B, c, m = features.shape
         n = idx.shape[1]
         out = torch.empty(B, c, n, dtype=torch.float32, device=features.device)
-        L.check(L.lib().pq3d_three_interpolate(L.ptr(features), L.ptr(idx), L.ptr(weight), L.ptr(out), B, c, m, n, L.stream()),
-                "pq3d_three_interpolate")
+        L.call("pq3d_three_interpolate", features, idx, weight, out, B, c, m, n)
         ctx.three_interpolate_for_backward = (idx, weight, m)
         return out
 
@@ -104,8 +99,7 @@ class ThreeInterpolate(Function):
         g = _f(grad_out)
         B, c, n = g.shape
         gf = torch.empty(B, c, m, dtype=torch.float32, device=g.device)
-        L.check(L.lib().pq3d_three_interpolate_grad(L.ptr(g), L.ptr(idx), L.ptr(weight), L.ptr(gf), B, c, m, n, L.stream()),
-                "pq3d_three_interpolate_grad")
+        L.call("pq3d_three_interpolate_grad", g, idx, weight, gf, B, c, m, n)
         return gf, None, None
 
 
@@ -121,8 +115,7 @@ class GroupingOperation(Function):
         B, C, N = features.shape
         _, npoint, nsample = idx.shape
         out = torch.empty(B, C, npoint, nsample, dtype=torch.float32, device=features.device)
-        L.check(L.lib().pq3d_gather_points(L.ptr(features), L.ptr(idx), L.ptr(out), B, C, N, npoint * nsample, L.stream()),
-                "pq3d_gather_points")
+        L.call("pq3d_gather_points", features, idx, out, B, C, N, npoint * nsample)
         ctx.for_backwards = (idx, N)
         return out
 
@@ -132,8 +125,7 @@ class GroupingOperation(Function):
         g = _f(grad_out)
         B, C = g.shape[:2]
         gf = torch.empty(B, C, N, dtype=torch.float32, device=g.device)
-        L.check(L.lib().pq3d_gather_points_grad(L.ptr(g), L.ptr(idx), L.ptr(gf), B, C, N, idx.shape[1] * idx.shape[2],
-                                                L.stream()), "pq3d_gather_points_grad")
+        L.call("pq3d_gather_points_grad", g, idx, gf, B, C, N, idx.shape[1] * idx.shape[2])
         return gf, None
 
 
@@ -149,8 +141,7 @@ class BallQuery(Function):
         B, N, _ = xyz.shape
         M = new_xyz.shape[1]
         idx = torch.empty(B, M, nsample, dtype=torch.int32, device=xyz.device)
-        L.check(L.lib().pq3d_ball_query(L.ptr(new_xyz), L.ptr(xyz), L.ptr(idx), B, N, M, float(radius), int(nsample),
-                                        L.stream()), "pq3d_ball_query")
+        L.call("pq3d_ball_query", new_xyz, xyz, idx, B, N, M, float(radius), int(nsample))
         ctx.mark_non_differentiable(idx)
         return idx
 

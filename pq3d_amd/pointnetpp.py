@@ -34,16 +34,15 @@ def group_rows(xyz, new_xyz, feats, feat_channels: int, idx, np_: int, ns: int, 
     if feat_channels:
         assert feats.stride(-1) == 1 and feats.stride(0) == N * feats.stride(1)
         fs = feats.stride(1)
-    L.check(L.lib().pq3d_group_rows(L.ptr(xyz), L.ptr(new_xyz), L.ptr(feats) if feat_channels else None,
-                                    L.dt_of(feats) if feat_channels else 0, fs, L.ptr(idx), L.ptr(out), L.dt_of(out), B, N,
-                                    feat_channels, np_, ns, Kp, L.stream()), "pq3d_group_rows")
+    L.call("pq3d_group_rows", xyz, new_xyz, feats if feat_channels else None, L.dt_of(feats) if feat_channels else 0, fs, idx, out,
+           L.dt_of(out), B, N, feat_channels, np_, ns, Kp)
     return out
 
 
 def group_maxpool(rows, G: int, ns: int) -> torch.Tensor:
     C = rows.shape[-1]
     out = torch.empty(G, C, dtype=rows.dtype, device=rows.device)
-    L.check(L.lib().pq3d_group_maxpool(L.ptr(rows), L.ptr(out), L.dt_of(rows), G, ns, C, L.stream()), "pq3d_group_maxpool")
+    L.call("pq3d_group_maxpool", rows, out, L.dt_of(rows), G, ns, C)
     return out
 
 

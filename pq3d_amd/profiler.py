@@ -1,8 +1,8 @@
 """Opt-in per-kernel-family timing with HIP events on the launch stream (bench.py's roofline section).
 
-`with KernelTimer() as t:` makes every C-ABI call issued through pq3d_amd._lib record an event pair on torch's
-current stream (the stream the kernels are launched on); `t.summary()` synchronises once and aggregates
-(calls, total ms, algorithmic FLOPs / bytes) per (entry point, shape key)."""
+`with KernelTimer() as t:` makes every `_lib.call(name, ..., work=(key, flops, bytes))` record an event pair on torch's
+current stream (the stream the kernels are launched on); launches issued without `work=` are not timed.  `t.summary()`
+synchronises once and aggregates (calls, total ms, algorithmic FLOPs / bytes) per (entry point, shape key)."""
 from __future__ import annotations
 
 from collections import defaultdict

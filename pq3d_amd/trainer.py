@@ -16,7 +16,6 @@ into the flat buffer (``p.data`` becomes a view), and the fused executor writes 
 flat gradient buffer, which is also what the data-parallel all-reduce operates on."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Dict, Optional, Sequence
 
 import torch
@@ -169,16 +168,14 @@ class TrainStep:
         return sg
 
     def optimizer_step(self) -> None:
-        n, s = self.flat_g.numel(), L.stream()
+        n = self.flat_g.numel()
         # parameters without a gradient in THIS step (a host-side fact of the autograd graph, also under graph capture):
         # skipped like torch.optim.AdamW does; their flat gradient is zero (pack), so the clip norm ignores them too
         missing = frozenset(id(p) for p in self.reducer.params if p.grad is None) if self._world() == 1 else frozenset()
         segs = self._segments(missing)
-        L.check(L.lib().pq3d_sumsq_partials(L.ptr(self.flat_g), n, L.ptr(self.partials), s), "pq3d_sumsq_partials")
-        L.check(L.lib().pq3d_train_scalars(C.byref(self.hp), L.ptr(self.step_count), L.ptr(self.partials),
-                                           L.ptr(self.scalars), s), "pq3d_train_scalars")
-        L.check(L.lib().pq3d_adamw(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                   n, C.byref(self.hp), C.byref(segs), L.ptr(self.scalars), s), "pq3d_adamw")
+        L.call("pq3d_sumsq_partials", self.flat_g, n, self.partials)
+        L.call("pq3d_train_scalars", self.hp, self.step_count, self.partials, self.scalars)
+        L.call("pq3d_adamw", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, n, self.hp, segs, self.scalars)
 
     def step(self, data_dict) -> torch.Tensor:
         """One full training step; returns the (detached) loss.  grad norm / lr of the step: ``self.scalars``.

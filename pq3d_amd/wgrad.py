@@ -5,7 +5,6 @@ the same launch, and the queue that defers products to a few grouped launches.  
 theirs: the split-K cap, the max(2, .) floor, and whether the one-launch flush must pay for itself (tt_multi_pays)."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Sequence
 
@@ -13,7 +12,6 @@ import torch
 
 from . import _lib as L
 from ._lib import BF16
-from .profiler import timed
 
 MAXG = L.MAXG
 # PQ3D_DETERMINISTIC=1: reductions that have an order-independent form take it (today: bias-gradient column sums of long
@@ -79,12 +77,10 @@ def dw_operands(gs, xs, x2s, N: int, K: int, R: int, ct: int):
     x2 = [conv(t, t2) for t, t2 in zip(xs, x2s)]
     if any(t is None for t in g2 + x2):
         return gs, xs, (x2s if any(t is not None for t in x2s) else None)
-    arr = lambda ts: (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])
     for n, lst in jobs.items():
         for s0 in range(0, len(lst), MAXG):
             ch = lst[s0:s0 + MAXG]
-            L.check(L.lib().pq3d_add_cast(arr([a for a, _, _ in ch]), arr([b for _, b, _ in ch]), arr([o for _, _, o in ch]),
-                                          len(ch), L.BF16, n, L.stream()), "pq3d_add_cast")
+            L.call("pq3d_add_cast", *(L.parr([j[k] for j in ch]) for k in range(3)), len(ch), L.BF16, n)
     return g2, x2, None
 
 
@@ -113,11 +109,8 @@ def _colsum_acc(xs: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], rows: 
             cur[0].append(xt); cur[1].append(ot); seen.add(ot.data_ptr())
         batches.append(cur)
         for xc, oc in batches:
-            xa = (C.c_void_p * len(xc))(*[L.ptr(t) for t in xc])
-            oa = (C.c_void_p * len(oc))(*[L.ptr(t) for t in oc])
             # accumulate = 2: the one-writer (bit-reproducible) form at every row count; 1 lets long columns add row slices atomically
-            L.check(L.lib().pq3d_colsum_grouped(xa, oa, len(xc), L.dt_of(xc[0]), rows * nblk, N, N, 2 if DETERMINISTIC else 1,
-                                                L.stream()), "pq3d_colsum_grouped")
+            L.call("pq3d_colsum_grouped", L.parr(xc), L.parr(oc), len(xc), L.dt_of(xc[0]), rows * nblk, N, N, 2 if DETERMINISTIC else 1)
 
 
 def launch(gs, xs, x2s, dws, dbs, ct: int, cap: int, *, min2: bool = True, accumulate: bool = True, alpha: float = 1.0) -> None:
@@ -187,8 +180,7 @@ def tt_multi(problems) -> None:
             fl += 2.0 * N * K * R
             nb += float(g.numel() * g.element_size() + x.numel() * x.element_size() + (x2.numel() * x2.element_size() if x2 is not None else 0)
                         + N * K * 4 + (N * 4 if db is not None else 0))   # compulsory: both operands once, the fp32 result (+ bias gradient)
-        L.check(timed("pq3d_gemm_tt_multi", f"ttmulti{len(ch)}", fl, nb, L.lib().pq3d_gemm_tt_multi, arr, len(ch), L.stream()),
-                "pq3d_gemm_tt_multi")
+        L.call("pq3d_gemm_tt_multi", arr, len(ch), work=(f"ttmulti{len(ch)}", fl, nb))
 
 
 class Queue:

@@ -36,53 +36,104 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.pq3d_version() >= 1
 
 
+def header_text():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def ctypes_structs():
+    """{normalised name: class} of every ctypes.Structure the binding defines ('pq3d_adamw_hp' and AdamWHp -> 'adamwhp')."""
+    return {n.lower(): c for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == _lib.__name__}
+
+
+def header_structs():
+    """{normalised name: typedef name} of every struct the header defines."""
+    return {t[len("pq3d_"):].replace("_", ""): t for t in re.findall(r"}\s*(pq3d_\w+)\s*;", header_text())}
+
+
 def test_struct_layouts_match_header(tmp_path):
-    """Compile a tiny C program against the header and compare sizeof/offsetof with the ctypes Structures."""
+    """Every Structure of the binding against the header's struct of the same name: sizeof, and offsetof / sizeof of every field,
+    from a C program generated from the ctypes classes and compiled against the header."""
+    ours, theirs = ctypes_structs(), header_structs()
+    assert sorted(ours) == sorted(theirs) and len(ours) >= 18, "ctypes binding and header disagree on the set of structs"
+    lines, want = [], []
+    for key in sorted(ours):
+        cls, ctype = ours[key], theirs[key]
+        lines.append(f'  printf("{ctype} %zu\\n", sizeof({ctype}));')
+        want.append(f"{ctype} {ctypes.sizeof(cls)}")
+        for name, *_ in cls._fields_:
+            lines.append(f'  printf("{ctype}.{name} %zu %zu\\n", offsetof({ctype}, {name}), sizeof((({ctype}*)0)->{name}));')
+            want.append(f"{ctype}.{name} {getattr(cls, name).offset} {getattr(cls, name).size}")
     csrc = tmp_path / "layout.c"
-    csrc.write_text(r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "pq3d_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_gemm_desc), offsetof(pq3d_gemm_desc, alpha), offsetof(pq3d_gemm_desc, A),
-         offsetof(pq3d_gemm_desc, mask_out));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_attn_desc), offsetof(pq3d_attn_desc, scale), offsetof(pq3d_attn_desc, q),
-         offsetof(pq3d_attn_desc, dbias));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_ln_desc), offsetof(pq3d_ln_desc, eps), offsetof(pq3d_ln_desc, x),
-         offsetof(pq3d_ln_desc, dbeta));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_ffn_desc), offsetof(pq3d_chain_ffn_desc, eps2), offsetof(pq3d_chain_ffn_desc, o_s),
-         offsetof(pq3d_chain_ffn_desc, err));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_ca_desc), offsetof(pq3d_chain_ca_desc, eps), offsetof(pq3d_chain_ca_desc, o),
-         offsetof(pq3d_chain_ca_desc, err));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_ffn_bwd_desc), offsetof(pq3d_chain_ffn_bwd_desc, F), offsetof(pq3d_chain_ffn_bwd_desc, dx),
-         offsetof(pq3d_chain_ffn_bwd_desc, err));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_sa_bwd_desc), offsetof(pq3d_chain_sa_bwd_desc, dqkv), offsetof(pq3d_chain_sa_bwd_desc, coef),
-         offsetof(pq3d_chain_sa_bwd_desc, err));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_mh_desc), offsetof(pq3d_chain_mh_desc, fill), offsetof(pq3d_chain_mh_desc, Wq),
-         offsetof(pq3d_chain_mh_desc, err));
-  printf("%zu %zu %zu %zu\n", sizeof(pq3d_chain_mh_bwd_desc), offsetof(pq3d_chain_mh_bwd_desc, dc), offsetof(pq3d_chain_mh_bwd_desc, dq),
-         offsetof(pq3d_chain_mh_bwd_desc, gq));
-  return 0;
-}''')
+    csrc.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pq3d_hip.h"\nint main(void) {\n' + "\n".join(lines) +
+                    "\n  return 0;\n}\n")
     exe = tmp_path / "layout"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(csrc), "-o", str(exe)])
-    rows = [list(map(int, l.split())) for l in subprocess.check_output([str(exe)]).decode().splitlines()]
-    G, A, Ln = _lib.GemmDesc, _lib.AttnDesc, _lib.LnDesc
-    assert rows[0] == [ctypes.sizeof(G), G.alpha.offset, G.A.offset, G.mask_out.offset]
-    assert rows[1] == [ctypes.sizeof(A), A.scale.offset, A.q.offset, A.dbias.offset]
-    assert rows[2] == [ctypes.sizeof(Ln), Ln.eps.offset, Ln.x.offset, Ln.dbeta.offset]
-    Ch = _lib.ChainFfnDesc
-    assert rows[3] == [ctypes.sizeof(Ch), Ch.eps2.offset, Ch.o_s.offset, Ch.err.offset]
-    Ca = _lib.ChainCaDesc
-    assert rows[4] == [ctypes.sizeof(Ca), Ca.eps.offset, Ca.o.offset, Ca.err.offset]
-    Cb = _lib.ChainFfnBwdDesc
-    assert rows[5] == [ctypes.sizeof(Cb), Cb.F.offset, Cb.dx.offset, Cb.err.offset]
-    Cs = _lib.ChainSaBwdDesc
-    assert rows[6] == [ctypes.sizeof(Cs), Cs.dqkv.offset, Cs.coef.offset, Cs.err.offset]
-    Cm = _lib.ChainMhDesc
-    assert rows[7] == [ctypes.sizeof(Cm), Cm.fill.offset, Cm.Wq.offset, Cm.err.offset]
-    Cn = _lib.ChainMhBwdDesc
-    assert rows[8] == [ctypes.sizeof(Cn), Cn.dc.offset, Cn.dq.offset, Cn.gq.offset]
+    got = subprocess.check_output([str(exe)]).decode().splitlines()
+    assert len(got) == len(want) > 400
+    assert [g for g, w in zip(got, want) if g != w] == [], "header layout (listed) differs from the ctypes Structure"
+
+
+def _c_param(decl: str):
+    """One parameter of a header prototype -> ('ptr', typedef name or None) | ('int' | 'float', bytes)."""
+    words = re.findall(r"\w+", decl.replace("*", " "))[:-1]     # the last word is the parameter's name
+    base = [w for w in words if w != "const"]
+    if "*" in decl:
+        return ("ptr", base[0] if decl.count("*") == 1 and base[0].startswith("pq3d_") else None)
+    return {"int": ("int", 4), "int32_t": ("int", 4), "uint32_t": ("int", 4), "int64_t": ("int", 8), "float": ("float", 4),
+            "double": ("float", 8)}[" ".join(base)]
+
+
+def _ctypes_param(t):
+    if t is ctypes.c_void_p or t is ctypes.c_char_p:
+        return ("ptr", None)
+    if isinstance(getattr(t, "_type_", None), type):             # POINTER(x)
+        to = t._type_
+        return ("ptr", header_structs()[to.__name__.lower()] if issubclass(to, ctypes.Structure) else None)
+    assert issubclass(t, ctypes._SimpleCData), t
+    return ("float" if t._type_ in "fd" else "int", ctypes.sizeof(t))
+
+
+def test_prototypes_match_header(lib):
+    """Every prototype of the header against the argtypes / restype the binding gives ctypes: number of arguments, pointer or
+    scalar (and, for a descriptor, which struct), scalar width, float or integer, and the width of the return value."""
+    protos = re.findall(r"\b(const char\s*\*|int64_t|int32_t|int)\s+(pq3d_\w+)\s*\(([^)]*)\)\s*;", header_text())
+    assert sorted(n for _r, n, _a in protos) == header_functions() == sorted(_lib.EXPORTS) and len(protos) >= 120
+    assert _lib._RET64 <= set(_lib._SIGS)
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        want_ret = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64}.get(ret, ctypes.c_char_p)
+        assert fn.restype is want_ret and (name in _lib._RET64) == (ret == "int64_t"), f"{name}: return type"
+        params = [] if params.strip() == "void" else [_c_param(p) for p in params.split(",")]
+        if name not in _lib._SIGS:
+            assert name in ("pq3d_last_error", "pq3d_version") and not params and not fn.argtypes, name
+            continue
+        assert fn.argtypes == _lib._SIGS[name]
+        assert [_ctypes_param(t) for t in _lib._SIGS[name]] == params, f"{name}: argument list differs from the header"
+
+
+def test_call_reports_argument_errors(lib):
+    """_lib.call: descriptor by reference, explicit stream, and the library's error text under the entry point's name."""
+    d = _lib.GemmDesc()
+    d.groups, d.batch, d.M, d.N, d.K = 999, 1, 4, 4, 4
+    with pytest.raises(_lib.Pq3dError, match=r"^pq3d_gemm failed \(rc=-1\): .*groups"):
+        _lib.call("pq3d_gemm", d, stream=0)
+    with pytest.raises(_lib.Pq3dError, match="not a launch entry point"):
+        _lib.call("pq3d_segment_plan_bytes", 1, 1, stream=0)
+
+
+def test_call_rejects_cpu_tensors_before_the_library(lib, monkeypatch):
+    import torch
+    fn, ptrs, by_ref = _lib._ENTRY.get("pq3d_colsum") or _lib._entry("pq3d_colsum")
+    entered = []
+    monkeypatch.setitem(_lib._ENTRY, "pq3d_colsum", (lambda *a: entered.append(a) or 0, ptrs, by_ref))
+    x, out = torch.zeros(4, 4), torch.zeros(4)
+    for args in ((x, _lib.F32, 4, 4, 4, None), (None, _lib.F32, 4, 4, 4, out)):
+        with pytest.raises(_lib.Pq3dError, match="device tensors"):
+            _lib.call("pq3d_colsum", *args, stream=0)
+    assert not entered
+    _lib.call("pq3d_colsum", None, _lib.F32, 4, 4, 4, None, stream=0)     # (the spy does see a call that passes)
+    assert len(entered) == 1 and entered[0][-1] == 0
 
 
 def test_argument_errors_are_reported(lib):

@@ -10,6 +10,13 @@ of synthetic scenes (BASELINE config 2: B=8 scenes/GPU, N_seg=1024, N_q=100, d=2
 parallel cross-attention, spatial self-attention, 2-D padding masks, loss = mean(query)), bf16 MFMA operands with
 fp32 accumulation, inputs resident in HBM, followed by the data-parallel gradient exchange (flat-buffer RCCL
 all-reduce, N > 1).  The step is captured once into a HIP graph and replayed.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the result line.  With
+--full the line also carries everything else the benchmark measures, each in passes of its own behind the timed steps: the
+per-kernel attribution and `roofline` (eager profiled pass + child kernel trace), the eager / drop-in / train-mode-dropout /
+compute-mode (`parity_modes`) / optimizer legs, the caption body alone and `cpu_baseline`:
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
 """
 from __future__ import annotations
 
@@ -324,7 +331,7 @@ def live_kernel_trace(args, timeout=300):
     tmp = tempfile.mkdtemp(prefix="pq3d_trace_", dir="/tmp")
     cmd = [exe, "--kernel-trace", "-d", tmp, "-o", "t", "--", sys.executable, os.path.abspath(__file__), "--config", args.config,
            "--compute", args.compute, "--dropout", args.dropout, "--steps", "20", "--warmup", "5", "--cpu-steps", "0", "--profile-steps", "1",
-           "--headline-only", "--min-time", "0", "--no-live-trace"] + (["--no-graph"] if args.no_graph else [])
+           "--full", "--headline-only", "--min-time", "0", "--no-live-trace"] + (["--no-graph"] if args.no_graph else [])
     try:
         t0 = time.perf_counter()
         subprocess.run(cmd, env=dict(os.environ, PQ3D_BENCH_CHILD="1", TMPDIR="/tmp"), cwd="/tmp", stdout=subprocess.DEVNULL,
@@ -468,6 +475,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline measurement run everything else the benchmark reports, each in passes of its own "
+                         "behind the timed steps: per-kernel attribution + roofline, the eager / drop-in / dropout / compute-mode / "
+                         "optimizer legs, the caption body alone, the CPU baseline (off by default: a plain run sets up, warms "
+                         "up, times --steps steps and prints the line)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + ["pool"],
                     help="c2 = the BASELINE metric's configuration (default); pool = segment pooling alone (bench_pool.py)")
     ap.add_argument("--pool-nvox", type=int, default=250_000, help="--config pool: voxels per scene")
@@ -475,34 +487,37 @@ def main():
     ap.add_argument("--pool-segments", type=int, default=4096, help="--config pool: segments per scene (max_seg)")
     ap.add_argument("--compute", default=DEFAULT_COMPUTE, choices=["bf16", "bf16x3", "fp32"])
     ap.add_argument("--no-live-trace", action="store_true",
-                    help="skip the child rocprofv3 --kernel-trace run that times the kernels of the replayed step for `roofline`")
+                    help="--full: skip the child rocprofv3 --kernel-trace run that times the kernels of the replayed step for "
+                         "`roofline`")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--min-time", type=float, default=0.0,
                     help="when K timed steps take < 0.5 s, repeat the K-step region until this many seconds are timed in "
                          "total (median over repeats reported; 0 = default: a single K-step region, exactly --steps timed steps)")
     ap.add_argument("--max-repeats", type=int, default=400)
-    ap.add_argument("--cpu-steps", type=int, default=32, help="timed CPU-baseline steps (0 disables)")
-    ap.add_argument("--profile-steps", type=int, default=3)
-    ap.add_argument("--dump-kernels", default=None, help="write the per-(entry point, shape) timing table here")
+    ap.add_argument("--cpu-steps", type=int, default=32, help="--full: timed CPU-baseline steps (0 disables)")
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: steps of the eager profiled pass")
+    ap.add_argument("--dump-kernels", default=None, help="--full: write the per-(entry point, shape) timing table here")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps write what the last timed step computed (model outputs, loss, every parameter "
                          "gradient) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (seeded samples beyond that)")
     ap.add_argument("--pmc-calibration", action="store_true",
-                    help="after the profiled pass launch ONE known streaming copy (100 MiB in, 100 MiB out, 16 B / lane): "
+                    help="--full: after the profiled pass launch ONE known streaming copy (100 MiB in, 100 MiB out, 16 B / lane): "
                          "under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE its raw counters calibrate the traffic numbers")
     ap.add_argument("--dropout", default="off", choices=["off", "reference"],
                     help="headline run: 'off' = p=0 (the parity-checked arithmetic); 'reference' = the reference's "
                          "train-mode probabilities (0.1 in the decoder layers and encoders, 0.1/0.3 in the heads)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline measurement + roofline pass (no eager / dropout / optimizer legs); what the "
+                    help="--full: only the headline measurement + roofline pass (no eager / dropout / optimizer legs); what the "
                          "rocprofv3 runs under profiles/ use so that the trace holds the headline step only")
     ap.add_argument("--no-optimizer-leg", action="store_true",
-                    help="skip the extra full-training-step (with optimizer) timing reported next to the headline")
+                    help="--full: skip the extra full-training-step (with optimizer) timing reported next to the headline")
     ap.add_argument("--no-parity-leg", action="store_true",
-                    help="skip the bf16-vs-fp32 compute-type comparison (parity_modes) reported next to the headline (N=1 only)")
+                    help="--full: skip the bf16-vs-fp32 compute-type comparison (parity_modes) reported next to the headline (N=1 only)")
     ap.add_argument("--no-dropout-leg", action="store_true",
-                    help="skip the extra train-mode-dropout timing reported next to the headline (N=1 only)")
+                    help="--full: skip the extra train-mode-dropout timing reported next to the headline (N=1 only)")
     args = ap.parse_args()
+    if not args.full and (args.dump_kernels or args.pmc_calibration):
+        ap.error("--dump-kernels and --pmc-calibration belong to the profiled pass: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, one process per GPU (the reference launches its own
@@ -869,92 +884,6 @@ def main():
     if rank == 0:
         flops = step_flops(c)
         peak = PEAK_BF16_TFLOPS if args.compute in ("bf16", "bf16x3") else PEAK_F32_TFLOPS
-        # per-kernel attribution: eager profiled pass with HIP events on the launch stream (rank 0 alone: no collectives)
-        enc.grads_ready, enc.grad_bucket_per_layer = None, False
-        with KernelTimer() as kt:
-            for _ in range(args.profile_steps):
-                fwd_bwd()
-        summ = kt.summary()
-        if args.pmc_calibration:
-            n_cal = CALIBRATION_BYTES // 4
-            csrc, cdst = torch.ones(n_cal, device=dev), torch.empty(n_cal, device=dev)
-            ops.copy_many([cdst], [csrc])
-            torch.cuda.synchronize()
-            del csrc, cdst
-        ps = max(args.profile_steps, 1)
-        tot = sum(v["ms"] for v in summ.values())
-        fams = {}
-        for (n, _k), v in summ.items():
-            f = fams.setdefault(n, dict(ms=0.0, calls=0, flops=0.0, bytes=0.0))
-            for kk in ("ms", "calls", "flops", "bytes"):
-                f[kk] += v[kk]
-        # ---- roofline of the run's real dominant KERNEL: time = in-graph kernel durations of THIS run (a child
-        # rocprofv3 --kernel-trace of the same build / box / config), work = the algorithmic bytes / FLOPs of the C-ABI calls that
-        # launch the kernel (this run's eager profiled pass), traffic = the committed PMC passes IF they are of this build
-        from pq3d_amd.build import build_ids
-        ids = build_ids()
-        pmc, mfma, cstats, pinfo = committed_profiles(args.config, args.compute, ids)
-        trace, tmeta = ({}, "not the single-GPU headline run") if (world > 1 or dist_on) else live_kernel_trace(args)
-        timing_src = "live"
-        if not trace and cstats:
-            trace, tmeta, timing_src = cstats, {"source": f"committed {pinfo.get('kernel_stats_file')} of this build (src_sha256 {ids['src_sha256']})"}, "committed"
-        blocks = []
-        if trace:
-            order = sorted(trace, key=lambda n: -trace[n][1])
-            blocks = [kernel_block(n, trace, summ, ps, peak, pmc, mfma) for n in order[:4] if not n.startswith("__amd_rocclr")][:3]
-            ktot = sum(v[1] for v in trace.values())
-            for b_ in blocks:
-                b_["share_of_kernel_time"] = trace[b_["kernel"]][1] / ktot if ktot else 0.0
-                if timing_src == "committed":
-                    b_["timing"] = "in-graph kernel durations, " + tmeta["source"]
-                if cstats and b_["kernel"] in cstats and timing_src == "live":   # the committed summary of the same build must agree
-                    b_["committed_profile_avg_launch_us"] = cstats[b_["kernel"]][1] / max(cstats[b_["kernel"]][0], 1e-9)
-        else:
-            # no trace (rocprofv3 absent / child failed): this run's own HIP-event times per C-ABI entry point, stated as such
-            order = sorted(fams, key=lambda n: -fams[n]["ms"])
-            for n in order[:3]:
-                v = fams[n]
-                t = v["ms"] / ps * 1e-3
-                tf, gbs = v["flops"] / ps / t / 1e12, v["bytes"] / ps / t / 1e9
-                blk = {"kernel": n, "gpu_kernels": FAMILY_KERNELS.get(n, []), "launches_per_step": v["calls"] / ps,
-                       "avg_launch_us": v["ms"] / v["calls"] * 1e3, "ms_per_step": v["ms"] / ps,
-                       "timing": "HIP events on the launch stream around each C-ABI call, eager profiled pass of this run (includes launch gaps)",
-                       "frac_mfma": tf / peak, "frac_hbm": gbs / PEAK_HBM_GBS, "traffic": None}
-                blk.update({"bound": "mfma", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak} if tf / peak >= gbs / PEAK_HBM_GBS
-                           else {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS})
-                blocks.append(blk)
-        roof = blocks[0] if blocks else {"kernel": None, "bound": "mfma", "achieved": 0.0, "peak": peak, "unit": "TFLOP/s", "frac": 0.0, "traffic": None}
-        roof["kernel_ms_per_step_eager_events"] = tot / ps
-        roof["trace"] = tmeta
-        roof["build"] = ids
-        if pinfo["refused"]:
-            roof["stale_profiles_refused"] = pinfo["refused"]
-        # step level: measured memory-side bytes of ALL kernels of a step (PMC passes of this build x in-graph launch counts) against
-        # SURVEY 8(d)'s closed-form compulsory bytes (ideal fusion: nothing but weights, memories and the query state moves)
-        step_alg_bytes = step_bytes(c)
-        step_traffic = None
-        if pmc is not None and trace:
-            tb = 0.0
-            for n, (lps, _us) in trace.items():
-                pl, _c = pmc_per_launch(pmc, n)
-                if pl is not None:
-                    tb += pl * lps
-            step_traffic = {"measured_traffic_bytes": tb, "algorithmic_bytes_survey_8d": step_alg_bytes,
-                            "traffic_over_algorithmic": tb / step_alg_bytes, "sustained_gbs": tb / (ms * 1e-3) / 1e9,
-                            "source": pmc.get("_file"), "note": "sum over every kernel of the step: calibrated FETCH_SIZE + WRITE_SIZE per "
-                            "launch x launches per step of the in-graph trace"}
-        else:
-            step_traffic = {"measured_traffic_bytes": None, "algorithmic_bytes_survey_8d": step_alg_bytes, "traffic_over_algorithmic": None,
-                            "note": "no PMC passes of this build under profiles/ (tools/refresh_profiles.sh writes them)"}
-        if args.dump_kernels:
-            with open(args.dump_kernels, "w") as f:
-                f.write(f"{'entry point':18s} {'shape':44s} {'calls/step':>10s} {'us/launch':>10s} {'ms/step':>8s} "
-                        f"{'TFLOP/s':>8s} {'GB/s':>8s}\n")
-                for (n, k), v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"]):
-                    us = v["ms"] / v["calls"] * 1e3
-                    f.write(f"{n:18s} {k:44s} {v['calls'] / args.profile_steps:10.1f} {us:10.1f} "
-                            f"{v['ms'] / args.profile_steps:8.3f} {v['flops'] / v['calls'] / us / 1e6:8.2f} "
-                            f"{v['bytes'] / v['calls'] / us / 1e3:8.1f}\n")
         result = {
             "metric": "decoder fwd+bwd scenes/sec at (N_seg=1024,N_q=100,d=256,L=4)" if args.config == "c2"
             else f"decoder fwd+bwd scenes/sec ({args.config})",
@@ -987,12 +916,97 @@ def main():
             **({"grads_identical_across_ranks": grads_identical, "grad_fingerprint_per_bucket": grad_fingerprint,
                 "collective_backend": backend,
                 "rccl_ranks": (torch.distributed.get_world_size() if backend == "nccl" else 0)} if dist_on else {}),
-            "roofline": roof,
-            "roofline_next": blocks[1:],
-            "step_traffic": step_traffic,
-            "kernel_families_ms_per_step": {k: round(v["ms"] / ps, 4) for k, v in sorted(fams.items())},
         }
-        if world == 1 and not dist_on and not args.headline_only:
+        if args.full:
+            # per-kernel attribution: eager profiled pass with HIP events on the launch stream (rank 0 alone: no collectives)
+            enc.grads_ready, enc.grad_bucket_per_layer = None, False
+            with KernelTimer() as kt:
+                for _ in range(args.profile_steps):
+                    fwd_bwd()
+            summ = kt.summary()
+            if args.pmc_calibration:
+                n_cal = CALIBRATION_BYTES // 4
+                csrc, cdst = torch.ones(n_cal, device=dev), torch.empty(n_cal, device=dev)
+                ops.copy_many([cdst], [csrc])
+                torch.cuda.synchronize()
+                del csrc, cdst
+            ps = max(args.profile_steps, 1)
+            tot = sum(v["ms"] for v in summ.values())
+            fams = {}
+            for (n, _k), v in summ.items():
+                f = fams.setdefault(n, dict(ms=0.0, calls=0, flops=0.0, bytes=0.0))
+                for kk in ("ms", "calls", "flops", "bytes"):
+                    f[kk] += v[kk]
+            # ---- roofline of the run's real dominant KERNEL: time = in-graph kernel durations of THIS run (a child
+            # rocprofv3 --kernel-trace of the same build / box / config), work = the algorithmic bytes / FLOPs of the C-ABI calls that
+            # launch the kernel (this run's eager profiled pass), traffic = the committed PMC passes IF they are of this build
+            from pq3d_amd.build import build_ids
+            ids = build_ids()
+            pmc, mfma, cstats, pinfo = committed_profiles(args.config, args.compute, ids)
+            trace, tmeta = ({}, "not the single-GPU headline run") if (world > 1 or dist_on) else live_kernel_trace(args)
+            timing_src = "live"
+            if not trace and cstats:
+                trace, tmeta, timing_src = cstats, {"source": f"committed {pinfo.get('kernel_stats_file')} of this build (src_sha256 {ids['src_sha256']})"}, "committed"
+            blocks = []
+            if trace:
+                order = sorted(trace, key=lambda n: -trace[n][1])
+                blocks = [kernel_block(n, trace, summ, ps, peak, pmc, mfma) for n in order[:4] if not n.startswith("__amd_rocclr")][:3]
+                ktot = sum(v[1] for v in trace.values())
+                for b_ in blocks:
+                    b_["share_of_kernel_time"] = trace[b_["kernel"]][1] / ktot if ktot else 0.0
+                    if timing_src == "committed":
+                        b_["timing"] = "in-graph kernel durations, " + tmeta["source"]
+                    if cstats and b_["kernel"] in cstats and timing_src == "live":   # the committed summary of the same build must agree
+                        b_["committed_profile_avg_launch_us"] = cstats[b_["kernel"]][1] / max(cstats[b_["kernel"]][0], 1e-9)
+            else:
+                # no trace (rocprofv3 absent / child failed): this run's own HIP-event times per C-ABI entry point, stated as such
+                order = sorted(fams, key=lambda n: -fams[n]["ms"])
+                for n in order[:3]:
+                    v = fams[n]
+                    t = v["ms"] / ps * 1e-3
+                    tf, gbs = v["flops"] / ps / t / 1e12, v["bytes"] / ps / t / 1e9
+                    blk = {"kernel": n, "gpu_kernels": FAMILY_KERNELS.get(n, []), "launches_per_step": v["calls"] / ps,
+                           "avg_launch_us": v["ms"] / v["calls"] * 1e3, "ms_per_step": v["ms"] / ps,
+                           "timing": "HIP events on the launch stream around each C-ABI call, eager profiled pass of this run (includes launch gaps)",
+                           "frac_mfma": tf / peak, "frac_hbm": gbs / PEAK_HBM_GBS, "traffic": None}
+                    blk.update({"bound": "mfma", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak} if tf / peak >= gbs / PEAK_HBM_GBS
+                               else {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS})
+                    blocks.append(blk)
+            roof = blocks[0] if blocks else {"kernel": None, "bound": "mfma", "achieved": 0.0, "peak": peak, "unit": "TFLOP/s", "frac": 0.0, "traffic": None}
+            roof["kernel_ms_per_step_eager_events"] = tot / ps
+            roof["trace"] = tmeta
+            roof["build"] = ids
+            if pinfo["refused"]:
+                roof["stale_profiles_refused"] = pinfo["refused"]
+            # step level: measured memory-side bytes of ALL kernels of a step (PMC passes of this build x in-graph launch counts) against
+            # SURVEY 8(d)'s closed-form compulsory bytes (ideal fusion: nothing but weights, memories and the query state moves)
+            step_alg_bytes = step_bytes(c)
+            step_traffic = None
+            if pmc is not None and trace:
+                tb = 0.0
+                for n, (lps, _us) in trace.items():
+                    pl, _c = pmc_per_launch(pmc, n)
+                    if pl is not None:
+                        tb += pl * lps
+                step_traffic = {"measured_traffic_bytes": tb, "algorithmic_bytes_survey_8d": step_alg_bytes,
+                                "traffic_over_algorithmic": tb / step_alg_bytes, "sustained_gbs": tb / (ms * 1e-3) / 1e9,
+                                "source": pmc.get("_file"), "note": "sum over every kernel of the step: calibrated FETCH_SIZE + WRITE_SIZE per "
+                                "launch x launches per step of the in-graph trace"}
+            else:
+                step_traffic = {"measured_traffic_bytes": None, "algorithmic_bytes_survey_8d": step_alg_bytes, "traffic_over_algorithmic": None,
+                                "note": "no PMC passes of this build under profiles/ (tools/refresh_profiles.sh writes them)"}
+            if args.dump_kernels:
+                with open(args.dump_kernels, "w") as f:
+                    f.write(f"{'entry point':18s} {'shape':44s} {'calls/step':>10s} {'us/launch':>10s} {'ms/step':>8s} "
+                            f"{'TFLOP/s':>8s} {'GB/s':>8s}\n")
+                    for (n, k), v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"]):
+                        us = v["ms"] / v["calls"] * 1e3
+                        f.write(f"{n:18s} {k:44s} {v['calls'] / args.profile_steps:10.1f} {us:10.1f} "
+                                f"{v['ms'] / args.profile_steps:8.3f} {v['flops'] / v['calls'] / us / 1e6:8.2f} "
+                                f"{v['bytes'] / v['calls'] / us / 1e3:8.1f}\n")
+            result.update({"roofline": roof, "roofline_next": blocks[1:], "step_traffic": step_traffic,
+                           "kernel_families_ms_per_step": {k: round(v["ms"] / ps, 4) for k, v in sorted(fams.items())}})
+        if args.full and world == 1 and not dist_on and not args.headline_only:
             # the same step launched eagerly (no HIP graph): what a trainer that cannot capture graphs would see
             def timed_loop(fn, n):
                 torch.cuda.synchronize()
@@ -1113,7 +1127,7 @@ def main():
                     "optimizer": "AdamW(betas=(0.9,0.98), wd 0.01) + clip_grad_norm_(80) + warmup_cosine, 3 kernels on "
                                  "one flat fp32 buffer", "params": int(ts.flat_p.numel()),
                     "finite": bool(torch.isfinite(ts.flat_p).all())}
-        if world == 1 and not dist_on and "generation" in c["heads"] and not args.headline_only:
+        if args.full and world == 1 and not dist_on and "generation" in c["heads"] and not args.headline_only:
             # the third-party body alone (fwd + bwd of the head on a detached query), eager
             gh = model.generation_head
             qd = torch.randn(c["B"], c["Nq"], c["d"], device=dev, requires_grad=True)
@@ -1127,7 +1141,7 @@ def main():
                                  "impl": "T5-small decoder (random init, HF parameter layout) restated on the HIP kernels "
                                          "(pq3d_amd/t5.py) + input_proj; teacher-forced, T_r = %d" % c["Tr"],
                                  "params": sum(p.numel() for p in gh.parameters())}
-        if world == 1 and not dist_on and args.cpu_steps > 0:
+        if args.full and world == 1 and not dist_on and args.cpu_steps > 0:
             hf_body = None
             if "generation" in c["heads"]:
                 import copy

@@ -5,7 +5,7 @@ A "step" = the voxel -> segment pooling of one batch of B = 4 scenes at the 5 de
 batch are sorted once (pq3d_segment_plan), every level is reduced over that grouping through the composed fine -> coarse
 index (the up-sampled [N, C] intermediate of the reference never exists), the gradient of the full-resolution level is a row
 gather and the gradients of the 4 coarse levels are the same reduction regrouped by the coarse parent.  Inputs are resident
-in HBM.  Beside the step, the plain torch_scatter.scatter_mean(feat [N, C], ids) -- every row really streamed from HBM --
+in HBM.  Beside the step, with --full, the plain torch_scatter.scatter_mean(feat [N, C], ids) -- every row really streamed from HBM --
 is swept over N_vox in {5e4, 2.5e5} per scene and C in {96, 128, 256}; the roofline block is that kernel at N_vox = 2.5e5,
 C = 256 on SURVEY 8d's algorithmic bytes N*C*4 + N*8 + S*C*4, timed live with HIP events on the launch stream."""
 from __future__ import annotations
@@ -125,77 +125,9 @@ def run(args, dev, world, rank, barrier, dist_on):
     if rank != 0:
         return None
 
-    # ---- per-kernel figures (HIP events on the launch stream), rank 0 ---------------------------------------------------
     def alg_bytes(n, s, c):
         return n * c * 4.0 + n * 8.0 + s * c * 4.0
 
-    plan = ops.SegmentPlan(idx, S)
-    t_plan = _ev_time(lambda: ops.SegmentPlan(idx, S), 20)
-    levels = []
-    for h in range(5):
-        c = LEVEL_C[h]
-        src = feats[h].detach()
-        if h < 4:
-            t_f = _ev_time(lambda: plan.reduce(src, parents[h], None, c, True), 20)
-            pplan = plan.child(parents[h], n_coarse[h])
-            inv = torch.ones(S, device=dev)
-            t_b = _ev_time(lambda: pplan.reduce(douts[h], idx, inv, c, False, want_count=False), 20)
-        else:
-            t_f = _ev_time(lambda: plan.reduce(src, None, None, c, True), 20)
-            cnt = torch.ones(S, device=dev)
-            t_b = _ev_time(lambda: ops.segment_gather(douts[h], idx, cnt), 20)
-        levels.append({"level": h, "C": c, "rows_read": int(src.shape[0]), "fwd_us": t_f, "bwd_us": t_b,
-                       "fwd_alg_gbs": alg_bytes(N, S, c) / t_f / 1e3, "bwd_alg_gbs": alg_bytes(N, S, c) / t_b / 1e3})
-    sweep = []
-    roof = None
-    bitexact = True
-    for nv in (50_000, 250_000):
-        n_, s_ = B * nv, S
-        ids_ = synth_ids(B, nv, max_seg, 7).to(dev)
-        pl = ops.SegmentPlan(ids_, s_)
-        for c in (96, 128, 256):
-            x = torch.randn(n_, c, device=dev)
-            t_f = _ev_time(lambda: pl.reduce(x, None, None, c, True), 30)
-            dy = torch.randn(s_, c, device=dev)
-            cnt = torch.ones(s_, device=dev)
-            t_b = _ev_time(lambda: ops.segment_gather(dy, ids_, cnt), 30)
-            a, _ = pl.reduce(x, None, None, c, True)
-            b2, _ = pl.reduce(x, None, None, c, True)
-            bitexact = bitexact and bool(torch.equal(a, b2))
-            row = {"n_vox_per_scene": nv, "N": n_, "S": s_, "C": c, "scatter_mean_fwd_us": t_f,
-                   "fwd_alg_gbs": alg_bytes(n_, s_, c) / t_f / 1e3, "fwd_frac_hbm": alg_bytes(n_, s_, c) / t_f / 1e3 / PEAK_HBM_GBS,
-                   "scatter_mean_bwd_us": t_b, "bwd_alg_gbs": alg_bytes(n_, s_, c) / t_b / 1e3,
-                   "bwd_frac_hbm": alg_bytes(n_, s_, c) / t_b / 1e3 / PEAK_HBM_GBS}
-            sweep.append(row)
-            if nv == 250_000 and c == 256:
-                roof = {"kernel": "segment_reduce_kernel<4,1> (pq3d_segment_reduce: scatter_mean forward, plain rows)",
-                        "bound": "hbm", "achieved": row["fwd_alg_gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                        "frac": row["fwd_frac_hbm"], "traffic": None, "avg_launch_us": t_f,
-                        "algorithmic_bytes_per_launch": alg_bytes(n_, s_, c),
-                        "shape": f"N = {n_} voxels (B = {B} x {nv}), S = {s_} segments, C = {c} fp32",
-                        "timing": "HIP events on the launch stream, 30 launches after 3 warm-up, this run",
-                        "bit_identical_run_to_run": None}
-            del x, dy
-    roof["bit_identical_run_to_run"] = bitexact
-    # measured memory-side traffic of that very launch: committed rocprofv3 --pmc passes (tools/pool_profile.sh), corrected by
-    # the calibration copy of the same pass as MI355X_MICROARCH.md's HBM section prescribes
-    import glob
-    pmcs = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_traffic_r*_pool.json")))
-    if pmcs:
-        try:
-            pj = json.load(open(pmcs[-1]))
-            rows = pj["kernels"].get("segment_reduce_kernel", [])
-            cal = pj.get("calibration") or {}
-            cf = 1.0 / cal["fetch_raw_over_true"] if cal.get("fetch_raw_over_true") else 2.0
-            cw = 1.0 / cal["write_raw_over_true"] if cal.get("write_raw_over_true") else 1.0
-            if rows:
-                r0 = max(rows, key=lambda r: r["launches"])
-                roof["traffic"] = (r0["fetch_kib"] * cf + r0["write_kib"] * cw) * 1024
-                roof["traffic_over_algorithmic"] = roof["traffic"] / roof["algorithmic_bytes_per_launch"]
-                roof["traffic_source"] = "profiles/" + os.path.basename(pmcs[-1])
-                roof["traffic_correction"] = {"fetch_x": round(cf, 3), "write_x": round(cw, 3)}
-        except (ValueError, KeyError):
-            pass
     step_bytes = sum(2 * alg_bytes(N, S, c) for c in LEVEL_C)
     result = {
         "metric": "segment pooling fwd+bwd scenes/sec (5 backbone levels, B=4)", "value": B * world * args.steps / dt,
@@ -206,9 +138,78 @@ def run(args, dev, world, rank, barrier, dist_on):
                                f"per scene, levels C={list(LEVEL_C)}, plan (sort) + 5 level means fwd + 5 gradients per step",
                    "global_batch": B * world, "parallelism": f"dp{world}", "hip_graph": False},
         "step_algorithmic_bytes": step_bytes, "step_alg_gbs": step_bytes / (dt / args.steps) / 1e9,
-        "plan_us": t_plan, "levels": levels, "scatter_mean_sweep": sweep, "roofline": roof,
     }
-    if args.cpu_steps > 0 and world == 1:
+    if args.full:
+        # ---- per-kernel figures (HIP events on the launch stream), rank 0 ---------------------------------------------------
+        plan = ops.SegmentPlan(idx, S)
+        t_plan = _ev_time(lambda: ops.SegmentPlan(idx, S), 20)
+        levels = []
+        for h in range(5):
+            c = LEVEL_C[h]
+            src = feats[h].detach()
+            if h < 4:
+                t_f = _ev_time(lambda: plan.reduce(src, parents[h], None, c, True), 20)
+                pplan = plan.child(parents[h], n_coarse[h])
+                inv = torch.ones(S, device=dev)
+                t_b = _ev_time(lambda: pplan.reduce(douts[h], idx, inv, c, False, want_count=False), 20)
+            else:
+                t_f = _ev_time(lambda: plan.reduce(src, None, None, c, True), 20)
+                cnt = torch.ones(S, device=dev)
+                t_b = _ev_time(lambda: ops.segment_gather(douts[h], idx, cnt), 20)
+            levels.append({"level": h, "C": c, "rows_read": int(src.shape[0]), "fwd_us": t_f, "bwd_us": t_b,
+                           "fwd_alg_gbs": alg_bytes(N, S, c) / t_f / 1e3, "bwd_alg_gbs": alg_bytes(N, S, c) / t_b / 1e3})
+        sweep = []
+        roof = None
+        bitexact = True
+        for nv in (50_000, 250_000):
+            n_, s_ = B * nv, S
+            ids_ = synth_ids(B, nv, max_seg, 7).to(dev)
+            pl = ops.SegmentPlan(ids_, s_)
+            for c in (96, 128, 256):
+                x = torch.randn(n_, c, device=dev)
+                t_f = _ev_time(lambda: pl.reduce(x, None, None, c, True), 30)
+                dy = torch.randn(s_, c, device=dev)
+                cnt = torch.ones(s_, device=dev)
+                t_b = _ev_time(lambda: ops.segment_gather(dy, ids_, cnt), 30)
+                a, _ = pl.reduce(x, None, None, c, True)
+                b2, _ = pl.reduce(x, None, None, c, True)
+                bitexact = bitexact and bool(torch.equal(a, b2))
+                row = {"n_vox_per_scene": nv, "N": n_, "S": s_, "C": c, "scatter_mean_fwd_us": t_f,
+                       "fwd_alg_gbs": alg_bytes(n_, s_, c) / t_f / 1e3, "fwd_frac_hbm": alg_bytes(n_, s_, c) / t_f / 1e3 / PEAK_HBM_GBS,
+                       "scatter_mean_bwd_us": t_b, "bwd_alg_gbs": alg_bytes(n_, s_, c) / t_b / 1e3,
+                       "bwd_frac_hbm": alg_bytes(n_, s_, c) / t_b / 1e3 / PEAK_HBM_GBS}
+                sweep.append(row)
+                if nv == 250_000 and c == 256:
+                    roof = {"kernel": "segment_reduce_kernel<4,1> (pq3d_segment_reduce: scatter_mean forward, plain rows)",
+                            "bound": "hbm", "achieved": row["fwd_alg_gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                            "frac": row["fwd_frac_hbm"], "traffic": None, "avg_launch_us": t_f,
+                            "algorithmic_bytes_per_launch": alg_bytes(n_, s_, c),
+                            "shape": f"N = {n_} voxels (B = {B} x {nv}), S = {s_} segments, C = {c} fp32",
+                            "timing": "HIP events on the launch stream, 30 launches after 3 warm-up, this run",
+                            "bit_identical_run_to_run": None}
+                del x, dy
+        roof["bit_identical_run_to_run"] = bitexact
+        # measured memory-side traffic of that very launch: committed rocprofv3 --pmc passes (tools/pool_profile.sh), corrected by
+        # the calibration copy of the same pass
+        import glob
+        pmcs = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_traffic_r*_pool.json")))
+        if pmcs:
+            try:
+                pj = json.load(open(pmcs[-1]))
+                rows = pj["kernels"].get("segment_reduce_kernel", [])
+                cal = pj.get("calibration") or {}
+                cf = 1.0 / cal["fetch_raw_over_true"] if cal.get("fetch_raw_over_true") else 2.0
+                cw = 1.0 / cal["write_raw_over_true"] if cal.get("write_raw_over_true") else 1.0
+                if rows:
+                    r0 = max(rows, key=lambda r: r["launches"])
+                    roof["traffic"] = (r0["fetch_kib"] * cf + r0["write_kib"] * cw) * 1024
+                    roof["traffic_over_algorithmic"] = roof["traffic"] / roof["algorithmic_bytes_per_launch"]
+                    roof["traffic_source"] = "profiles/" + os.path.basename(pmcs[-1])
+                    roof["traffic_correction"] = {"fetch_x": round(cf, 3), "write_x": round(cw, 3)}
+            except (ValueError, KeyError):
+                pass
+        result.update({"plan_us": t_plan, "levels": levels, "scatter_mean_sweep": sweep, "roofline": roof})
+    if args.full and args.cpu_steps > 0 and world == 1:
         from oracle import pq3d_oracle as O   # CPU baseline leg only: the oracle's restatement of torch_scatter's definition
         ncpu = os.cpu_count() or 1
         torch.set_num_threads(min(32, ncpu))

@@ -77,3 +77,14 @@ def test_dump_outputs_is_deterministic_typed_and_bounded(tmp_path, monkeypatch):
         assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f.name
     w = np.load(tmp_path / "a" / "grad.w.npy")
     assert 0 < w.size < 1_000_000 and np.isin(w, arrays["grad.w"].numpy()).all()
+
+
+def test_profiled_pass_options_need_full(monkeypatch, capsys):
+    """--dump-kernels / --pmc-calibration act inside the profiled pass, which only a --full run has: a plain run refuses them at the
+    command line (before it touches a device) instead of ignoring them."""
+    import pytest
+    for extra in (["--dump-kernels", "table.txt"], ["--pmc-calibration"]):
+        monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0"] + extra)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err

@@ -16,10 +16,10 @@ done
 F=$(find /tmp/pmc_FETCH_SIZE -name "*.db" | head -1); W=$(find /tmp/pmc_WRITE_SIZE -name "*.db" | head -1)
 python $R/tools/pmc_traffic_json.py $F $W > $OUT/pmc_traffic_${TAG}_pool.json && cp $OUT/pmc_traffic_${TAG}_pool.json $R/profiles/
 rm -rf /tmp/ks
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/ks -o s -- python $R/bench.py --config pool --steps 10 --warmup 3 --cpu-steps 0 > $OUT/bench_under_rocprof_pool.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/ks -o s -- python $R/bench.py --config pool --full --steps 10 --warmup 3 --cpu-steps 0 > $OUT/bench_under_rocprof_pool.json 2>/dev/null
 DB=$(find /tmp/ks -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $DB 1 > $OUT/rocprofv3_kernel_stats_${TAG}_pool.txt
 cp $OUT/rocprofv3_kernel_stats_${TAG}_pool.txt $R/profiles/
-timeout 600 python $R/bench.py --config pool --steps 20 --warmup 5 > $OUT/bench_${TAG}_pool_1gpu.json 2> $OUT/bench_pool.err
+timeout 600 python $R/bench.py --config pool --full --steps 20 --warmup 5 > $OUT/bench_${TAG}_pool_1gpu.json 2> $OUT/bench_pool.err
 cp $OUT/bench_${TAG}_pool_1gpu.json $R/profiles/
 echo done

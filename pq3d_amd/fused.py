@@ -29,7 +29,8 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from . import ops, wgrad
+from . import attn, ops, wgrad
+from .attn import sa_fold_ok
 from .wgrad import _colsum_acc  # noqa: F401  (importable from fused as before: tests/test_gpu_ops.py)
 from ._lib import BF16
 
@@ -205,53 +206,9 @@ def _ln_bwd(x, os_, gammas, betas, eps, coef, rows_per_scene, mean, rstd, dy, dg
     return dx, d_o
 
 
-def kv3_ks(Lk: int, dh: int = 32) -> int:
-    """Key splits of the split-bf16 cross-attention forward (csrc/attn_x3.hip: at most 1024 keys per workgroup at d_h = 32, 512 at
-    d_h = 64) -- a function of the key length only, like every forward split factor (a scene's result must not depend on how scenes
-    are batched)."""
-    return max(1, -(-((Lk + 63) // 64) // (16 if dh == 32 else 8)))
-
-
-def _attn(q, k, v, o, lse, H, ct, zero_attn, kpm=None, mask=None, row_open=None, bias=None, mask_bmod=0, bwd=None,
-          drop=None, drop_bmod=0, proj_dout=None, mask_bits=None, planes=None):
-    """proj_dout = (g, W): backward only -- dO = g W is formed inside the attention kernel (pq3d_attn_proj, DOUT) and
-    bwd[0] is ignored; the caller checks sa_fold_ok() first.
-    planes = (k_lo, v_lo, q_bf, o_bf): forward only, compute mode 'bf16x3' -- q / o fp32, k / v the hi planes (csrc/attn_x3.hip)."""
-    d = ops._attn_desc(q, k, v, o, lse, H, ct, zero_attn, 1.0 / math.sqrt(q.shape[-1] // H), kpm, mask, row_open, bias,
-                       drop, drop_bmod, bwd=bwd is not None, mask_bits=mask_bits)
-    d.mask_bmod = mask_bmod
-    B, Lq, dm = q.shape
-    Lk = k.shape[1]
-    if planes is not None:
-        assert bwd is None and ct == L.BF16X3 and q.dtype == torch.float32 and k.dtype == torch.bfloat16
-        d.k_lo, d.v_lo, d.q_bf, d.o_bf = map(L.ptr, planes)
-        ks = kv3_ks(Lk, dm // H)
-        d.ksplit, d.ws, d._ws_keepalive = 1, None, None
-        if ks > 1:
-            d._ws_keepalive = torch.empty(ks * B * H * Lq * (dm // H + 2), dtype=torch.float32, device=q.device)
-            d.ksplit, d.ws = ks, L.ptr(d._ws_keepalive)
-    key = f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}" + ("m3" if mask is not None else "")
-    if bwd is None:
-        L.call("pq3d_attn_fwd", d, work=(key, 4.0 * B * Lq * Lk * dm, (q.numel() * 2 + k.numel() * 2) * q.element_size()))
-    else:
-        d.dout, d.dq, d.dk, d.dv, d.delta, d.dbias = map(L.ptr, bwd)
-        if proj_dout is not None:
-            d.proj.mode, d.proj.dm, d.proj.x = 2, dm, L.ptr(proj_dout[0])
-            d.proj.w[0] = L.ptr(proj_dout[1])
-        L.call("pq3d_attn_bwd", d, work=(key, 8.0 * B * Lq * Lk * dm, (q.numel() * 3 + k.numel() * 4) * q.element_size()))
-
-
-def sa_fold_ok(ct, B, H, L_, dm, drop, df, W) -> bool:
-    """The split-bf16 self-attention backward kernel can form dO itself (attn_sa.hip): its shape limits + 160 KB of LDS."""
-    if ops.sa_ct(ct) != L.BF16X3 or dm != 32 * H or dm % 32 or drop is not None:
-        return False
-    if df.dtype != torch.float32 or W.dtype != torch.float32 or not df.is_contiguous() or not W.is_contiguous():
-        return False
-    if (df.data_ptr() | W.data_ptr()) & 15:
-        return False
-    lp2, lpk = (L_ + 31) & ~31, (L_ + 31) & ~31
-    lds = (4 * lp2 + 4 * lpk + dm) * 40 * 2 + (lpk + 2 * lp2) * 4 + 16
-    return L_ <= 240 and lds <= 160 * 1024
+def _attn(q, k, v, o, lse, H, ct, zero_attn, bwd=None, **kw):
+    """One attention launch of the fused pass: forward, or backward with bwd = (dout, dq, dk, dv, delta, dbias); keywords: attn.desc."""
+    (attn.fwd if bwd is None else attn.bwd)(q, k, v, o, lse, H, ct, zero_attn, key_m3=True, grads=bwd, **kw)
 
 
 class _PendingDx:

@@ -12,7 +12,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from . import wgrad
+from . import attn, wgrad
 from .wgrad import dw_long_path, tt_multi, tt_multi_ok  # noqa: F401  (the weight-gradient helpers, importable from ops as before)
 from ._lib import BF16, BF16X3, F32
 
@@ -630,67 +630,13 @@ def linear_group(xs, Ws, *, ct: int, out_dtype=torch.float32):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _attn_desc(q, k, v, o, lse, H, ct, zero_attn, scale, kpm, mask, row_open, bias, drop=None, drop_bmod=0,
-               bwd=False, mask_bits=None) -> L.AttnDesc:
-    B, Lq, dm = q.shape
-    Lk = k.shape[1]
-    d = L.AttnDesc()
-    d.B, d.H, d.Lq, d.Lk, d.dh = B, H, Lq, Lk, dm // H
-    d.ct, d.dt, d.zero_attn, d.scale = ct, L.dt_of(q), int(zero_attn), scale
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", o)):
-        assert t.stride(-1) == 1
-        setattr(d, name + "_sb", t.stride(0)); setattr(d, name + "_sl", t.stride(1)); setattr(d, name + "_sh", dm // H)
-    d.q, d.k, d.v, d.o, d.lse = L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(o), L.ptr(lse)
-    d.kpm, d.mask, d.row_open, d.bias = L.ptr(kpm), L.ptr(mask), L.ptr(row_open), L.ptr(bias)
-    d.mask_bits = L.ptr(mask_bits) if mask is not None else None
-    L.set_drop(d.drop, drop)
-    d.drop_bmod = drop_bmod
-    # key split (not with dbias).  The factor depends on the key length ONLY, never on the batch: a scene's result
-    # must not change with how scenes are batched or sharded over ranks (tests/test_gpu_fullsize.py).  Measured
-    # (tools/probes/attn_bench.py + bench.py): c2 (16 key blocks) and c5 (32) are fastest with 2 splits, c4 (64) with 4
-    # (forward 70 -> 57 us, step 5.56 -> 5.43 ms); 8 only adds combine traffic.
-    nkb = (Lk + 63) // 64
-    ks = (1 if nkb < 8 else 2 if nkb < 64 else 4) if bias is None else 1
-    if not bwd and ct == BF16 and q.dtype == torch.bfloat16 and bias is None and mask is None and \
-            Lq <= 128 <= Lk and dm // H == 32 and nkb <= 16:
-        # the all-keys-resident forward (attn_resident.hip) holds up to 1024 keys per workgroup: config 2 needs no split
-        # (and no combine launch).  Longer scenes keep the streaming kernel and its split (measured at config 5, 2048 keys:
-        # resident with 2 splits 63-76 us vs streaming 58 us) -- a function of the key length only, as above
-        ks = 1
-    if bwd and ks > 1 and ct == BF16 and bias is None and Lq <= 128 and (dm // H) in (32, 64) and \
-            (B * H >= 320 or (B * H <= 256 and Lk >= 512 and dm // H == 32)):
-        # the all-queries-resident backward (attn_resident.hip) runs one workgroup per (scene, head, slice): once the
-        # stacked batch alone fills the chip (config 5: 48 x 8) a second slice only adds dQ partials (85 -> 75 us).
-        # Gradients are summed with atomics downstream anyway, so this may depend on the batch; the forward's may not.
-        # At most one workgroup per CU (config 2: 24 x 8): the 8-wave variant of the kernel takes all keys of a (scene,
-        # head) -- no dQ partials, no combine launch.
-        ks = 1
-    if bwd and ks > 2 and ct == BF16 and bias is None and 128 < Lq <= 256 and dm // H == 32 and \
-            B * H * (ks // 2) <= 256 and Lk // (ks // 2) >= 512:
-        ks //= 2      # the 8-wave resident backward (two query halves, config 4): half the key slices, one workgroup per CU
-    if bwd and ct == BF16 and bias is None and Lq <= 128 and dm // H == 64 and nkb >= 16 and B * H * ks < 512:
-        # d_h = 64 resident backward (4 waves per workgroup, the shipped stage-1 decoder: 12 x 12 (scene, head) pairs,
-        # 2048 keys): at least two workgroups per CU -- measured 2 / 4 / 8 / 16 slices: 15.12 / 14.82 / 14.97 / 15.45 ms
-        ks = min(8, -(-512 // (B * H)))
-    if ks > 1:
-        ws = _empty(ks * B * H * Lq * (dm // H + 2), dtype=torch.float32, device=q.device)
-        d.ksplit, d.ws = ks, L.ptr(ws)
-        d._ws_keepalive = ws
-    return d
-
-
 class _Attention(Function):
     @staticmethod
     def forward(ctx, q, k, v, bias, kpm, mask, row_open, H, zero_attn, scale, ct, drop=None):
         q, k, v, bias, kpm, mask, row_open = map(_c, (q, k, v, bias, kpm, mask, row_open))
-        B, Lq, dm = q.shape
         o = _empty(q.shape, dtype=q.dtype, device=q.device)
-        lse = _empty(B, H, Lq, dtype=torch.float32, device=q.device)
-        d = _attn_desc(q, k, v, o, lse, H, ct, zero_attn, scale, kpm, mask, row_open, bias, drop)
-        Lk = k.shape[1]
-        fl = 4.0 * B * Lq * Lk * dm
-        nb = (q.numel() * 2 + k.numel() * 2) * q.element_size()
-        L.call("pq3d_attn_fwd", d, work=(f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb))
+        lse = _empty(q.shape[0], H, q.shape[1], dtype=torch.float32, device=q.device)
+        attn.fwd(q, k, v, o, lse, H, ct, zero_attn, scale=scale, kpm=kpm, mask=mask, row_open=row_open, bias=bias, drop=drop)
         ctx.save_for_backward(q, k, v, o, lse, bias, kpm, mask, row_open)
         ctx.cfg = (H, zero_attn, scale, ct)
         ctx.drop = drop
@@ -700,19 +646,10 @@ class _Attention(Function):
     def backward(ctx, do):
         q, k, v, o, lse, bias, kpm, mask, row_open = ctx.saved_tensors
         H, zero_attn, scale, ct = ctx.cfg
-        do = do.contiguous()
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        delta = torch.empty_like(lse)
+        dq, dk, dv, delta = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(lse)
         dbias = torch.empty_like(bias) if (bias is not None and ctx.needs_input_grad[3]) else None
-        d = _attn_desc(q, k, v, o, lse, H, ct, zero_attn, scale, kpm, mask, row_open, bias, ctx.drop, bwd=True)
-        d.dout, d.dq, d.dk, d.dv, d.delta, d.dbias = map(L.ptr, (do, dq, dk, dv, delta, dbias))
-        B, Lq, dm = q.shape
-        Lk = k.shape[1]
-        # ALGORITHMIC flops (backward = 2 x forward = 8 B Lq Lk d); the two recompute kernels EXECUTE 14:
-        # dQ kernel S, dP, dQ (6) + dK/dV kernel S, dP, dK, dV (8)
-        fl = 8.0 * B * Lq * Lk * dm
-        nb = (q.numel() * 3 + k.numel() * 4) * q.element_size()
-        L.call("pq3d_attn_bwd", d, work=(f"B{B}H{H}Lq{Lq}Lk{Lk}dh{dm // H}ct{ct}", fl, nb))
+        attn.bwd(q, k, v, o, lse, H, ct, zero_attn, grads=(do.contiguous(), dq, dk, dv, delta, dbias), scale=scale, kpm=kpm, mask=mask,
+                 row_open=row_open, bias=bias, drop=ctx.drop)
         return dq, dk, dv, dbias, None, None, None, None, None, None, None, None
 
 

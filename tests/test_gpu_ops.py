@@ -183,6 +183,31 @@ def test_attention_fully_masked_row_with_zero_attn_is_zero():
     assert float(o.abs().max()) == 0.0
 
 
+def test_attention_key_split_descriptor_on_strided_views():
+    """The smallest call that splits (fp32, 8 key blocks) on head-packed views cut out of wider buffers: the descriptor carries the
+    split, its workspace and the views' strides, and computes attention; with 7 key blocks it carries no split and no workspace."""
+    from pq3d_amd import attn
+    B, H, Lq, dh = 2, 2, 16, 32
+    d = H * dh
+    for Lk, split in ((512, True), (448, False)):
+        bufs = [rnd(B, L_ + 3, d, seed=s).to(DEV) for L_, s in ((Lq, 1), (Lk, 2), (Lk, 3))]
+        q, k, v = bufs[0][:, :Lq], bufs[1][:, 1:Lk + 1], bufs[2][:, 2:Lk + 2]    # batch stride (L + 3) d > L d
+        kpm = (torch.arange(Lk)[None, :] >= torch.tensor([Lk, Lk // 2])[:, None]).to(DEV)
+        o, lse = torch.empty(B, Lq, d, device=DEV), torch.empty(B, H, Lq, device=DEV)
+        dd, ws = attn.desc(q, k, v, o, lse, H, F32, True, kpm=kpm)
+        if split:
+            assert dd.ksplit == 2 and ws is not None and dd.ws == ws.data_ptr() and ws.numel() == attn.ws_elems(2, B, H, Lq, dh)
+        else:
+            assert dd.ksplit <= 1 and ws is None and not dd.ws
+        for name, t in (("q", q), ("k", k), ("v", v), ("o", o)):
+            assert not t.is_contiguous() or name == "o"
+            assert [getattr(dd, f"{name}_{x}") for x in ("sb", "sl", "sh")] == [t.stride(0), t.stride(1), dh], name
+        L.call("pq3d_attn_fwd", dd)
+        ref = attn_ref(*(t.double().cpu() for t in (q, k, v)), H, 1 / math.sqrt(dh), True, kpm.cpu(), None, None, None)
+        close(o, ref, F32, f"descriptor launch, Lk {Lk}")
+        close(ops.attention(q, k, v, H=H, ct=F32, zero_attn=True, kpm=kpm), ref, F32, f"ops.attention, Lk {Lk}")
+
+
 def test_mask_row_all():
     m = torch.rand(3, 17, 130) < 0.5
     m[1, 4] = True

@@ -26,7 +26,7 @@ def build_probe():
 
 def main():
     import torch
-    from pq3d_amd import _lib as L, fused
+    from pq3d_amd import _lib as L, attn, fused
     B, H, Lq, Lk, d = 24, 8, 100, 1024, 256
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
@@ -40,8 +40,7 @@ def main():
     delta = torch.empty(B, H, Lq, device=dev)
     ws = torch.zeros(16, dtype=torch.int64, device=dev)
     for it in range(300):
-        dd = fused.ops._attn_desc(q, k, v, o, lse, H, L.BF16, True, 1.0 / 32 ** 0.5, kpm, None, None, None, None, 0, bwd=True)
-        dd.dout, dd.dq, dd.dk, dd.dv, dd.delta, dd.dbias = map(L.ptr, (go, dq, dk, dv, delta, None))
+        dd, _ = attn.desc(q, k, v, o, lse, H, L.BF16, True, kpm=kpm, grads=(go, dq, dk, dv, delta, None))
         assert dd.ksplit <= 1, dd.ksplit
         dd.ws = L.ptr(ws)
         L.check(L.lib().pq3d_attn_bwd(L.C.byref(dd), L.stream()), "bwd")

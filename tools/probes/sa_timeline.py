@@ -27,7 +27,7 @@ def build_probe():
 
 def main():
     import torch
-    from pq3d_amd import _lib as L, fused
+    from pq3d_amd import _lib as L, attn, fused
     B, H, Lq, d = 8, 8, 100, 256
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
@@ -43,12 +43,9 @@ def main():
         ws = torch.zeros(16, dtype=torch.int64, device=dev)
         rows = []
         for it in range(300):   # back to back (clocks up); the stamps of the last launch are read
-            dd = fused.ops._attn_desc(q, k, v, o, lse, H, L.BF16X3, False, 1.0 / 32 ** 0.5, kpm, None, None, bias, None, 0, bwd=True)
-            dd.dout, dd.dq, dd.dk, dd.dv, dd.delta, dd.dbias = map(L.ptr, (None if fold else go, dqkv[0], dqkv[1], dqkv[2], delta, dsb))
+            dd, _ = attn.desc(q, k, v, o, lse, H, L.BF16X3, False, kpm=kpm, bias=bias, proj_dout=(go, W) if fold else None,
+                              grads=(None if fold else go, dqkv[0], dqkv[1], dqkv[2], delta, dsb))
             dd.ws = L.ptr(ws)
-            if fold:
-                dd.proj.mode, dd.proj.dm, dd.proj.x = 2, d, L.ptr(go)
-                dd.proj.w[0] = L.ptr(W)
             L.check(L.lib().pq3d_attn_bwd(L.C.byref(dd), L.stream()), "bwd")
         torch.cuda.synchronize()
         t = ws.cpu().tolist()

@@ -38,6 +38,8 @@ extern "C" {
 #define PQ3D_ACT_GELU 2
 
 #define PQ3D_MAX_GROUPS 32
+#define PQ3D_ACT_QGELU 5 /* act only, forward only: x * sigmoid(1.702 x) (CLIP's quick_gelu); the generic epilogue applies it, the
+                            kernels with an epilogue of their own decline the call */
 #define PQ3D_ACT_ADD 3 /* act_grad mode: C = acc + aux (fused residual / gradient accumulation) */
 #define PQ3D_ACT_PLANES 4 /* act_grad mode: v = act(alpha acc + bias) leaves as two bf16 planes, C = bf16(v), C2 = bf16(v - C)
                              (operand form of the split-bf16 attention, compute mode 'bf16x3'); plain bf16 NT products on the
@@ -1135,6 +1137,31 @@ int pq3d_t5_prep(const int64_t* labels, int64_t start_id, int64_t pad_id, const 
                  void* stream);
 int pq3d_t5_bias_bwd(const float* dbias, const int64_t* buckets, float* drel, int32_t B, int32_t T, int32_t H, int32_t NB,
                      int32_t accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pieces of the CLIP text prompt encoder (modules/language/clip.py: HF CLIPTextModelWithProjection, frozen; forward only)
+ * that the kernels above do not cover (pq3d_amd/csrc/clip_text.hip; host side pq3d_amd/clip_text.py).  dt_* are
+ * PQ3D_F32 / PQ3D_BF16; every tensor is dense and 16-byte aligned.
+ *   pq3d_clip_embed      : x[n, t, :] = tok[ids[n, t], :] + pos[t, :]   (tok [vocab, d], pos [>= T, d], both dt_tab; ids [n, T]
+ *                          int64; x dt_out).  An id outside [0, vocab) is CLAMPED to the nearest valid row (never a fault, never
+ *                          an error: the kernel cannot report one without a host round trip).
+ *   pq3d_attn_causal_fwd : self-attention of a short sequence over the PACKED output of one [3 d, d] projection:
+ *                          qkv [n, T, 3 H 64] (q | k | v, heads packed in the last dim), out [n, T, H 64], both dt.
+ *                          Key k is visible to query q iff k <= q and valid[n, k] != 0 (valid [n, T] bytes, any pattern; NULL =
+ *                          all valid).  Scores, softmax and the value contraction are fp32.  A query row with NO visible key
+ *                          writes zeros (HF's additive-mask softmax yields an implementation-defined uniform row there; it cannot
+ *                          occur when token 0 is valid, which CLIP's BOS always is).  d_h is fixed at 64 (every CLIP text tower);
+ *                          T <= PQ3D_ATTN_CAUSAL_MAX_T (K, V and the score tile of one (prompt, head) live in LDS): a larger T
+ *                          is refused with PQ3D_ERR_ARG and nothing is launched.
+ *   pq3d_l2norm_rows     : y[r, :] = x[r, :] / max(||x[r, :]||_2, eps)   (F.normalize(p=2); a zero row gives zeros)
+ * The quick-GELU of the tower's MLP is pq3d_gemm's PQ3D_ACT_QGELU epilogue.
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_ATTN_CAUSAL_MAX_T 77
+int pq3d_clip_embed(const void* tok, const void* pos, const int64_t* ids, void* x, int64_t n, int32_t T, int32_t d,
+                    int64_t vocab, int32_t dt_tab, int32_t dt_out, void* stream);
+int pq3d_attn_causal_fwd(const void* qkv, const uint8_t* valid, void* out, int32_t n, int32_t T, int32_t H, int32_t dt,
+                         float scale, void* stream);
+int pq3d_l2norm_rows(const void* x, void* y, int64_t R, int32_t d, int32_t dt_x, int32_t dt_y, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange over RCCL / xGMI (SURVEY 8b's export list: pq3d_comm_init, pq3d_allreduce_grads; 8e).

@@ -4,3 +4,10 @@ Host side is Python on PyTorch-ROCm (device memory, streams, torch.distributed o
 arithmetic runs in hand-written HIP kernels behind a C-ABI shared library (include/pq3d_hip.h).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):   # lazy: importing the package stays free of torch-side module construction
+    if name == "CLIPLanguageEncoder":
+        from .clip_text import CLIPLanguageEncoder
+        return CLIPLanguageEncoder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

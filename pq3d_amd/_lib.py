@@ -11,7 +11,7 @@ import torch
 from .profiler import timed
 
 F32, BF16, BF16X3 = 0, 1, 2
-ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "add": 3, "planes": 4}
+ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "add": 3, "planes": 4, "quick_gelu": 5}   # quick_gelu: forward only (act, never act_grad)
 MAXG = 32
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PQ3D_LIB_PATH") or os.path.join(_HERE, "libpq3d_hip.so")   # override: A/B builds of the kernels
@@ -353,6 +353,11 @@ _SIGS = {
     "pq3d_t5_prep": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p],
     "pq3d_t5_bias_bwd": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    # CLIP text prompt encoder (csrc/clip_text.hip)
+    "pq3d_clip_embed": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                        C.c_int32, C.c_void_p],
+    "pq3d_attn_causal_fwd": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p],
+    "pq3d_l2norm_rows": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p],
     # data-parallel gradient exchange over RCCL (csrc/comm.hip)
     "pq3d_comm_unique_id": [C.c_void_p],
     "pq3d_comm_init": [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],

@@ -129,6 +129,7 @@ PQ_DEV float load_elem(const void* base, int dt, long idx) {
 }
 
 PQ_DEV float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+PQ_DEV float qgelu_f(float x) { return x / (1.f + expf(-1.702f * x)); }   // x sigmoid(1.702 x): CLIP's quick_gelu (forward only)
 PQ_DEV float gelu_grad_f(float x) {
   return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }

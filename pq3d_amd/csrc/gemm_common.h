@@ -143,6 +143,9 @@ PQ_DEV void epi_row(const pq3d_kdesc& d, const GPtrs& gp, float (&v)[NV], int g,
   } else if (d.act == PQ3D_ACT_GELU) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = gelu_f(v[j]);
+  } else if (d.act == PQ3D_ACT_QGELU) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = qgelu_f(v[j]);
   }
   if (drop_on(d.drop)) {   // dropout of the activated output; col is even, so pairs never straddle threads
     const DropState ds = drop_init(d.drop, g, d.N);

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import modules as M
 from . import ops
+from .clip_text import CLIPLanguageEncoder
 
 
 class Cfg(dict):
@@ -31,7 +32,7 @@ class Cfg(dict):
 
 
 REGISTRY = {c.__name__: c for c in (M.QueryMaskEncoder, M.QueryEncoder, M.MaskHeadSegLevel, M.GroundHead, M.GroundHeadV1,
-                                    M.ObjectEncoder, M.T5, M.PCDMask3DSegLevelEncoder)}
+                                    M.ObjectEncoder, M.T5, M.PCDMask3DSegLevelEncoder, CLIPLanguageEncoder)}
 
 
 def _to_dict(c):
@@ -68,8 +69,9 @@ class Query3DUnified(nn.Module):
     """model/query3d_unified.py:30-238.  Supported inputs: offline voxel features (``use_offline_voxel_fts``),
     mv / pc segment features, and the prompt memory either pre-encoded (``data_dict['prompt_feat']`` [B,T,d]) or through
     ``prompt_encoder`` (``prompt`` / ``prompt_type`` / ``prompt_pad_masks``: 'loc' prompts on the HIP encoders, 'txt' prompts
-    through a caller-supplied ``txt_encoder`` -- the CLIP text encoder itself is out of scope).  Heads: 'mask', 'ground', 'generation' (input_proj on the HIP kernels, the HF T5
-    decoder body on stock PyTorch-ROCm ops, §8f-3)."""
+    through ``txt_encoder`` -- the CLIP text encoder on the HIP kernels (pq3d_amd/clip_text.py) when ``cfg.model.txt_encoder`` is
+    given, as in the reference; without it a caller may assign a module of its own).  Heads: 'mask', 'ground', 'generation'
+    (input_proj and the T5 decoder body on the HIP kernels, pq3d_amd/t5.py)."""
 
     def __init__(self, cfg, compute: str = "bf16"):
         super().__init__()
@@ -85,7 +87,12 @@ class Query3DUnified(nn.Module):
         self.skip_query_encoder_mask_pred = cfg.model.get("skip_query_encoder_mask_pred", False)
         for inp in self.inputs:
             if inp == "prompt":
-                continue  # text encoder out of scope: prompt memory arrives pre-encoded
+                # query3d_unified.py:47-53: the text prompt encoder, when configured ('loc' prompts use the coordinate
+                # encoders); without a cfg.model.txt_encoder the prompt memory arrives pre-encoded or through a
+                # caller-assigned model.txt_encoder
+                if cfg.model.get("txt_encoder") is not None:
+                    self.txt_encoder = build_module_by_name(cfg.model.get("txt_encoder"))
+                continue
             # voxel without use_offline_voxel_fts: the reference runs its MinkowskiEngine backbone inside the model
             # (query3d_unified.py:146-152); here the backbone is outside (out of scope) and the voxel encoder is the
             # post-backbone part (M.PCDMask3DSegLevelEncoder) fed the backbone's per-level features
@@ -132,8 +139,8 @@ class Query3DUnified(nn.Module):
     def prompt_encoder(self, data_dict):
         """query3d_unified.py:80-108: encode the prompt of every scene by its `prompt_type`.  'loc' prompts (the first dim_loc
         entries of the prompt row are a location) run through the coordinate / box encoders on the HIP kernels and occupy token 0
-        alone (`mask[:, 1:] = False`); 'txt' prompts are handed to ``self.txt_encoder`` -- the reference's CLIP text encoder is out
-        of scope, so a caller that trains with text prompts assigns its own module there (called as
+        alone (`mask[:, 1:] = False`); 'txt' prompts are handed to ``self.txt_encoder`` -- CLIPLanguageEncoder on the HIP kernels
+        when ``cfg.model.txt_encoder`` configures it (make_cfg(txt_encoder=...)), else a module the caller assigned there (called as
         ``encoder(token_ids.long(), pad_mask)`` -> [n, T, d], exactly as the reference calls it).  Like the reference, the
         scenes' `prompt_pad_masks` rows are updated IN PLACE; returns (prompt_feat [B, T, d], key-padding mask = ~pad mask)."""
         prompt, ppm, ptype = data_dict["prompt"], data_dict["prompt_pad_masks"], data_dict["prompt_type"]
@@ -146,8 +153,8 @@ class Query3DUnified(nn.Module):
             if kind == "txt":
                 enc = getattr(self, "txt_encoder", None)
                 if enc is None:
-                    raise NotImplementedError("text prompts need a text encoder: assign model.txt_encoder (the reference's CLIP "
-                                              "encoder is outside the hot path, SURVEY section 2) or pass data_dict['prompt_feat']")
+                    raise NotImplementedError("text prompts need a text encoder: configure cfg.model.txt_encoder (CLIPLanguageEncoder), "
+                                              "assign model.txt_encoder or pass data_dict['prompt_feat']")
                 feat = enc(inp.long(), mask)
             else:
                 loc = inp[:, :self.dim_loc].float()
@@ -330,14 +337,17 @@ class Query3DUnified(nn.Module):
             lr = get_lr(self.cfg.model.get(name), self.cfg.solver.lr)
             groups += no_decay_param_group(module.named_parameters(), lr, name=name)
         n = sum(len(g["params"]) for g in groups)
-        assert n == len(list(self.parameters())), "Some parameters are not optimized!"
+        # frozen parameters (the CLIP text tower: requires_grad False) are skipped by no_decay_param_group, as in the reference
+        assert n == sum(p.requires_grad for p in self.parameters()), "Some parameters are not optimized!"
         return groups
 
 
 def make_cfg(*, d, H, L, memories, heads, d_in=None, spatial=True, structure="parallel", use_self_mask=False,
              num_blocks=1, dim_loc=3, C=201, foc=(), drop_test=(), offline_attn=False, skip_pred=False,
-             activation="relu", ground_hidden=None, t5=None, memory_dropout=0.0) -> Cfg:
-    """Config with the reference YAML layout (configs/instseg_sceneverse.yaml:92-155) for synthetic runs."""
+             activation="relu", ground_hidden=None, t5=None, memory_dropout=0.0, txt_encoder=None) -> Cfg:
+    """Config with the reference YAML layout (configs/instseg_sceneverse.yaml:92-155) for synthetic runs.  txt_encoder: dict of
+    CLIPLanguageEncoder's constructor arguments (unified_tasks_sceneverse.yaml:122-127; ``hf_config`` sets the architecture
+    offline); None (default): no text encoder is built."""
     d_in = d_in or {m: d for m in memories}
     model = {"name": "Query3DUnified", "memories": list(memories), "heads": list(heads), "hidden_size": d,
              "use_offline_voxel_fts": True, "use_offline_attn_mask": offline_attn,
@@ -357,6 +367,8 @@ def make_cfg(*, d, H, L, memories, heads, d_in=None, spatial=True, structure="pa
         model["generation_head"] = {"name": "T5", "args": {"variant": "t5-small", "input_size": d,
                                                             "use_projection": True, **({"hf_config": t5} if t5 else {})},
                                     "lr": 1e-5}
+    if txt_encoder is not None:
+        model["txt_encoder"] = {"name": "CLIPLanguageEncoder", "args": dict(txt_encoder)}
     for m in memories:
         if m != "prompt":
             model[f"{m}_encoder"] = {"name": "ObjectEncoder", "args": {

@@ -482,6 +482,8 @@ class _Linear(Function):
     @staticmethod
     def backward(ctx, dy):
         x, x2, w, saved, rm, fill_flag = ctx.saved_tensors
+        if ctx.act == "quick_gelu":
+            raise L.Pq3dError("ops.linear(act='quick_gelu') is forward only (the frozen CLIP text tower): no backward")
         ct = bwd_ct(ctx.ct)
         N, K = w.shape
         R = x.numel() // K
@@ -549,6 +551,7 @@ def linear(x, w, b=None, *, ct: int, x2=None, act: Optional[str] = None, out_dty
            fill_flag=None, fill_value=0.0, drop: Optional[L.Drop] = None, residual=None, masked_grad: Optional[dict] = None):
     """y = act((x + x2) @ w.T + b); rows where row_mask == False are zeroed; rows where fill_flag == True are
     set to fill_value (masked_fill of whole rows); residual (same shape as y) is added in the GEMM epilogue.
+    act: None, 'relu', 'gelu', or 'quick_gelu' (x sigmoid(1.702 x), forward only: its backward raises).
     (F.linear call sites, see include/pq3d_hip.h)
     masked_grad: a hand-over slot shared with the rmsnorm that consumes y (``rmsnorm(..., grad_drop=(drop, slot))``): that
     norm's backward kernel also writes dropout_mask * dy / (1 - p), which this layer's backward then takes instead of

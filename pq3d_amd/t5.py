@@ -47,6 +47,13 @@ def shift_right(labels: torch.Tensor, start_id: int, pad_id: int) -> torch.Tenso
     return torch.where(ids == -100, torch.full_like(ids, pad_id), ids)
 
 
+def scales_decoder_output(cfg) -> bool:
+    """Whether HF multiplies the decoder output by d_model^-0.5 before the LM head.  transformers 5 always ties the
+    embeddings (config.tie_word_embeddings is forced True) and records a configured ``tie_word_embeddings=False`` as
+    ``scale_decoder_outputs = False``; earlier versions scale iff config.tie_word_embeddings."""
+    return bool(getattr(cfg, "scale_decoder_outputs", cfg.tie_word_embeddings))
+
+
 def decoder_logits(model, enc: torch.Tensor, enc_valid: Optional[torch.Tensor], labels: torch.Tensor, ct: int,
                    training: bool = False, drop_epoch_owner=None) -> torch.Tensor:
     """Teacher-forced logits [B, T, vocab] of the HF T5 model's decoder attending to ``enc`` [B, N, d_model]
@@ -123,7 +130,7 @@ def decoder_logits(model, enc: torch.Tensor, enc_valid: Optional[torch.Tensor], 
     gd, handover[0] = handover[0], None
     x = ops.rmsnorm(x, dec.final_layer_norm.weight, cfg.layer_norm_epsilon, grad_drop=gd)
     # final dropout and the tied-embedding scale d_model^-0.5 in one launch (either direction)
-    x = ops.dropout(x, next_drop(), alpha=(dm ** -0.5) if cfg.tie_word_embeddings else 1.0)
+    x = ops.dropout(x, next_drop(), alpha=(dm ** -0.5) if scales_decoder_output(cfg) else 1.0)
     return ops.linear(x, model.lm_head.weight, None, ct=ct)
 
 
@@ -232,7 +239,7 @@ class GreedyDecoder:
             hid = ops.linear(h, ff.DenseReluDense.wi.weight, None, ct=ct, act="relu", out_dtype=ad)
             x = ops.linear(hid, ff.DenseReluDense.wo.weight, None, ct=ct, residual=x)
         x = ops.rmsnorm(x, m.decoder.final_layer_norm.weight, eps)
-        if cfg.tie_word_embeddings:
+        if scales_decoder_output(cfg):
             x = x * (cfg.d_model ** -0.5)
         logits = ops.linear(x, m.lm_head.weight, None, ct=ct)                    # [B, 1, vocab]
         nxt = logits[:, 0].argmax(-1)

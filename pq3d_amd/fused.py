@@ -29,7 +29,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from . import attn, ops, wgrad
+from . import arena, attn, ops, wgrad
 from .attn import sa_fold_ok
 from .wgrad import _colsum_acc  # noqa: F401  (importable from fused as before: tests/test_gpu_ops.py)
 from ._lib import BF16
@@ -291,7 +291,7 @@ class _DecoderBackward(_DecoderPass):
             def ready(tag):
                 # weight gradients queued by ops.linear layers that ran backward BEFORE the decoder (heads)
                 # must be in their slots before an owner is told that a bucket is final
-                ops.dw_deferred_flush()
+                arena.dw_deferred_flush()
                 ready_cb(tag)
         else:
             ready = lambda tag: None
@@ -303,67 +303,13 @@ class _DecoderBackward(_DecoderPass):
 
     def _open_arena(self):
         """Gradient arena: every parameter gradient of the decoder is a view of a flat zeroed fp32 buffer (the data-parallel
-        reducer's / optimizer's, or one of this pass); decides fresh vs accumulating pass."""
-        enc, M, params, B, Nq, d, dev, n_app = self.enc, self.M, self.params, self.B, self.Nq, self.d, self.dev, self.n_app
-        # ---- gradient arena: one flat zeroed fp32 buffer, every parameter gradient is a view of it
-        sizes = [p.numel() for p in params]
-        ext = getattr(enc, "grad_arena", None)   # {id(param): (flat, offset, numel)} of a DP reducer's flat buffers
-        gv = {}
+        reducer's / optimizer's, or one of this pass); arena.open_decoder decides fresh vs accumulating pass."""
+        enc, M = self.enc, self.M
         # input gradients of the M-branch cross-attention LayerNorms are accumulated with atomics by the M branch blocks; that
         # buffer and the gradient arena are zeroed by ONE launch for the whole backward
-        dxr_zero = torch.empty(n_app, B, Nq, d, dtype=torch.float32, device=dev) if M > 1 else None
-        accumulate = False
-        in_place = ext is not None and all(id(p) in ext for p in params)
-        if in_place:
-            # gradients go straight into the owner's flat buffer (data-parallel bucket / optimizer arena): no pack copy.
-            for p in params:
-                flat, o_, n_ = ext[id(p)]
-                gv[id(p)] = flat[o_:o_ + n_].view(p.shape)
-            # torch semantics of a second backward before zero_grad: gradients ACCUMULATE (the reference trains under
-            # accelerator.accumulate, trainer/query3d_trainer.py:35).  Every parameter gradient of this backward is formed
-            # by accumulating launches (split-K atomics, accumulating column sums), so accumulation = not zeroing the arena.
-            # Which case this is is read off the parameters: .grad still aliasing the arena -> the owner has not consumed the
-            # previous micro-batch -> add in place (and hand autograd nothing: .grad already is the arena);
-            # .grad None / foreign everywhere -> fresh step: zero, then hand fresh views to autograd (adopted without a copy).
-            req = [p for p in params if p.requires_grad]
-            alias = [p.grad is not None and p.grad.data_ptr() == gv[id(p)].data_ptr() for p in req]
-            # parameters outside the decoder (the input encoders) with slots in the buffers zeroed here: offered to the
-            # backward functions that run after this one in the same pass (ops.arena_offer)
-            bufs = list(getattr(enc, "grad_arena_buffers", ()))
-            zeroed, own = {b.data_ptr() for b in bufs}, {id(p) for p in params}
-            offer = {}
-            for i_, q_ in getattr(ext, "params", {}).items():
-                if i_ not in own and q_.requires_grad and ext[i_][0].data_ptr() in zeroed:
-                    fl_, o_, n_ = ext[i_]
-                    offer[q_.data_ptr()] = (q_, fl_, o_, n_)
-            mixed = "fused decoder backward: some parameters' .grad alias the shared gradient arena and others do not -- " \
-                    "zero ALL gradients (set_to_none=True) or none between micro-batches"
-            if ops._Arena.whole_pass and ops._Arena.mode is not None and \
-                    all(p.data_ptr() in ops._Arena.by_ptr for p in req):
-                # the owner opened the arena around the whole pass (ops.grad_arena): already zeroed / accumulating
-                accumulate = ops._Arena.mode == "accumulate"
-                if accumulate and not all(alias):
-                    raise RuntimeError(mixed)
-                offer = {}
-                if not ops.arena_flush_zero([dxr_zero]):   # first consumer of a fresh pass: arena + own scratch, one launch
-                    ops.zero_many([dxr_zero])
-            elif req and all(alias):
-                accumulate = True
-                ops.zero_many([dxr_zero])
-            elif any(alias) or any(q_.grad is not None and q_.grad.data_ptr() == f_.data_ptr() + 4 * o_ for q_, f_, o_, n_ in offer.values()):
-                raise RuntimeError(mixed)
-            else:
-                ops.zero_many(bufs + [dxr_zero])
-            if offer:
-                ops.arena_offer(offer, "accumulate" if accumulate else "fresh")
-        else:
-            arena = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            ops.zero_many([arena, dxr_zero])
-            off = 0
-            for p, n in zip(params, sizes):
-                gv[id(p)] = arena[off:off + n].view(p.shape)
-                off += n
-        self.gv, self.dxr_zero, self.accumulate, self.in_place = gv, dxr_zero, accumulate, in_place
+        self.dxr_zero = torch.empty(self.n_app, self.B, self.Nq, self.d, dtype=torch.float32, device=self.dev) if M > 1 else None
+        self.gv, self.accumulate, self.in_place = arena.open_decoder(
+            getattr(enc, "grad_arena", None), getattr(enc, "grad_arena_buffers", ()), self.params, self.dxr_zero)
 
     def G(self, p):
         return self.gv[id(p)]

@@ -19,7 +19,7 @@ from typing import Dict, List, Sequence
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import arena, ops
 
 OUT_TENSORS = ("query_embeds", "ground_logits", "generation_logits", "generation_label")   # the label: long, no gradient
 OUT_LISTS = ("predictions_class", "predictions_mask")
@@ -230,8 +230,7 @@ class GraphedQuery3D(nn.Module):
 
     # -- backward body (captured twice: fresh / accumulating) ------------------------------------------------------------
     def _grad_view(self, p, delta: bool = False):
-        flat, off, n = (self._slots_delta if delta else self._slots)[id(p)]
-        return flat[off:off + n].view_as(p)
+        return (self._slots_delta if delta else self._slots).view(p)
 
     def _fresh_grad_views(self, delta: bool = False):
         """One NEW view object per parameter (None for the unreached ones), in parameter order: what mode 'autograd' hands to
@@ -262,24 +261,23 @@ class GraphedQuery3D(nn.Module):
         for p in params:
             p.grad = self._grad_view(p) if accumulate else None
         req = [o for o in outs if o.requires_grad]
-        with ops.grad_arena(slots, flats) as arena:   # every slot offered for the whole pass (zeroed here when fresh)
+        with arena.grad_arena(slots, flats) as pass_arena:   # every slot offered for the whole pass (zeroed here when fresh)
             grads = torch.autograd.grad(req, [self._args[i] for i in self._gin_idx] + params, grad_outputs=self.static_gout,
                                         allow_unused=True, retain_graph=retain)
         gin, gp = grads[:len(self._gin_idx)], grads[len(self._gin_idx):]
         if not accumulate:
-            arena.verify_returned(params, gp)   # tied weights: the returned gradient must still be the slot (ops.arena_verify)
+            pass_arena.verify_returned(params, gp)   # tied weights: the returned gradient must still be the slot (arena.verify)
         views, srcs = [], []
         for p, g in zip(params, gp):
-            v = self._grad_view(p, delta)
             if g is None:
                 if not accumulate:
                     # no gradient from autograd: either written in place by the fused executor in accumulate mode (never
                     # here) or genuinely unused -> zero in a fresh step, untouched when accumulating
-                    v.zero_()
+                    self._grad_view(p, delta).zero_()
                     if record_unused:
                         self._unused.add(id(p))
-            elif g.data_ptr() != v.data_ptr():
-                views.append(v); srcs.append(g)
+            elif not slots.holds(p, g):
+                views.append(self._grad_view(p, delta)); srcs.append(g)
         if views:
             (torch._foreach_add_ if accumulate else torch._foreach_copy_)(views, srcs)
         if (accumulate or delta) and self.static_gin is not None:   # input gradients land in the buffers of the fresh graph
@@ -296,10 +294,8 @@ class GraphedQuery3D(nn.Module):
 
     def _accumulating(self) -> bool:
         """True when every parameter's .grad still aliases its flat-buffer view (no zero_grad since the last backward)."""
-        ptrs = getattr(self, "_view_ptrs", None)
-        if ptrs is None:   # (parameter, address of its slot): cached -- a view per parameter per step was 0.3 ms of host time
-            ptrs = self._view_ptrs = [(p, self._grad_view(p).data_ptr()) for p in self._params if id(p) not in self._unused]
-        alias = [p.grad is not None and p.grad.data_ptr() == a for p, a in ptrs]
+        # (compares addresses: a view per parameter per step was 0.3 ms of host time)
+        alias = [self._slots.aliased(p) for p in self._params if id(p) not in self._unused]
         if all(alias) and alias:
             return True
         if any(alias):

@@ -12,7 +12,8 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from . import attn, wgrad
+from . import arena, attn, wgrad
+from .arena import dw_defer_exclude, dw_deferred_flush, grad_arena  # noqa: F401  (the gradient arena's public names, importable from ops as before)
 from .wgrad import dw_long_path, tt_multi, tt_multi_ok  # noqa: F401  (the weight-gradient helpers, importable from ops as before)
 from ._lib import BF16, BF16X3, F32
 
@@ -387,75 +388,6 @@ def mean_all(x: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ linear
-# ---- deferred weight gradients of a whole-pass gradient arena ------------------------------------------------------------
-# Inside ``with ops.grad_arena(...)`` every dW = g^T (x [+ x2]) of an arena-aware linear layer only feeds its slot of the flat
-# gradient buffer, so nothing waits for it: the products are queued per (shape, dtype) bucket and launched as a few GROUPED
-# split-K launches when the pass ends (grad_arena.__exit__) instead of one launch per layer -- the caption body's 46 launches of
-# [512 x 512] / [2048 x 512] products over 512 rows at config 5 are latency chains of ~15 us each.  The decoder's own backward
-# does the same for its layers with a queue of its own; this one serves everything that goes through ops.linear /
-# ops.linear_group around it.
-_DW_QUEUE = wgrad.Queue(split_x2=True)
-_DW_QUEUE_CAP = 256 << 20   # the deferral exists for the latency-bound small-R products; big operands are not held for long
-
-
-def _dw_can_defer(g, x, x2, N, K) -> bool:
-    if not _Arena.whole_pass or _Arena.mode is None:
-        return False
-    return not ((x2 is not None and (x2.dtype != torch.float32 or x.dtype != torch.float32)) or N % 8 or K % 8 or
-                g.data_ptr() % 16 or x.data_ptr() % 16 or (x2 is not None and x2.data_ptr() % 16) or
-                not g.is_contiguous() or not x.is_contiguous())
-
-
-_DW_NO_DEFER = set()    # id(param): never deferred (dw_defer_exclude)
-
-
-def dw_defer_exclude(params, on: bool = True) -> None:
-    """Exclude parameters from weight-gradient deferral.  REQUIRED for parameters whose gradient is read by a hook Python cannot see:
-    torch DDP's reducer registers its bucket hooks in C++ on the AccumulateGrad node (grad_accumulator->add_post_hook), which neither
-    Tensor._backward_hooks nor _post_accumulate_grad_hooks shows -- under a whole-pass gradient arena such a hook would read a slot
-    whose queued product only runs when the pass ends.  (The package's own data-parallel path, parallel.FlatGradAllReducer, flushes
-    the queue before a bucket leaves and needs no exclusion.)"""
-    for p in params:
-        (_DW_NO_DEFER.add if on else _DW_NO_DEFER.discard)(id(p))
-
-
-def _param_has_hooks(q) -> bool:
-    """Python-visible gradient hooks (tensor hooks, post-accumulate-grad hooks, Python hooks on the AccumulateGrad node) or an
-    explicit exclusion (dw_defer_exclude: C++-side hooks such as DDP's cannot be detected from here)."""
-    ent = _Arena.by_ptr.get(q)
-    if ent is None:
-        return False
-    p_ = ent[0]
-    if id(p_) in _DW_NO_DEFER or getattr(p_, "_backward_hooks", None) or getattr(p_, "_post_accumulate_grad_hooks", None):
-        return True
-    try:   # Python hooks registered on the parameter's AccumulateGrad node itself
-        acc = p_.view_as(p_).grad_fn.next_functions[0][0]
-        return bool(getattr(acc, "_post_hooks", None)) or bool(getattr(acc, "_pre_hooks", None))
-    except Exception:  # noqa: BLE001
-        return False
-
-
-def _dw_defer(g, x, x2, dw, db, N, K, ct, pptrs=()) -> bool:
-    """Queue dw[N, K] += g^T (x [+ x2]) (and db[N] += column sums of g); False when the pass has no whole-pass arena.
-    A parameter with Python-visible gradient hooks, or one listed through dw_defer_exclude (torch DDP: its C++ bucket hooks are
-    invisible from Python), is never deferred: its hook would read the slot before the queued product has run."""
-    if not _dw_can_defer(g, x, x2, N, K) or any(_param_has_hooks(q) for q in pptrs if q is not None):
-        return False
-    # the queue keeps its OWN view objects of the slots: AccumulateGrad adopts the returned gradient without a copy only when
-    # nobody else references that tensor object (arena_take) -- a second reference would turn .grad into a clone of zeros
-    _DW_QUEUE.add([g], [x], [x2], [dw.view(N, K)], ct, [db.view(-1)] if db is not None else None)
-    if _DW_QUEUE.nbytes > _DW_QUEUE_CAP:
-        dw_deferred_flush()
-    return True
-
-
-def dw_deferred_flush(run: bool = True) -> None:
-    """Launch (run=False: drop) the queued weight-gradient products.  Called when the pass ends (grad_arena.__exit__), from
-    the fused decoder's readiness reports, from FlatGradAllReducer.launch() / pack() -- no reader of a slot gets ahead of the
-    queue -- and when the queue holds more than _DW_QUEUE_CAP bytes of operands."""
-    _DW_QUEUE.flush(run)
-
-
 class _Linear(Function):
     @staticmethod
     def forward(ctx, x, w, b, x2, row_mask, ct, act, out_dtype, fill_flag, fill_value, drop=None, residual=None, masked_grad=None):
@@ -524,12 +456,12 @@ class _Linear(Function):
         if ctx.needs_input_grad[1]:
             fuse = want_db and wgrad.colsum_fusable([g], [x], [x2], N, K, ct)   # the bias gradient rides on the same launch
             # the owner's gradient arena, when offered for this pass: accumulate straight into the slots (pre-zeroed)
-            slot, give = arena_take([ctx.pptr[0]] + ([ctx.pptr[1]] if fuse else []), [N * K] + ([N] if fuse else []))
+            slot, give = arena.take([ctx.pptr[0]] + ([ctx.pptr[1]] if fuse else []), [N * K] + ([N] if fuse else []))
             if slot is not None:
                 dw, give_w = slot[0].view(N, K), give
                 if fuse:
                     db = slot[1]
-                if not (alpha == 1.0 and _dw_defer(g, x, x2, dw, db if fuse else None, N, K, ct, pptrs=ctx.pptr)):   # else: queued until the pass ends
+                if not (alpha == 1.0 and arena.defer(g, x, x2, dw, db if fuse else None, N, K, ct, pptrs=ctx.pptr)):   # else: queued until the pass ends
                     wgrad.launch([g], [x], [x2], [dw], [db] if fuse else None, ct, wgrad.SPLITK_CAP_LAYER, alpha=alpha)
             else:
                 dw = _empty(N, K, dtype=torch.float32, device=x.device)
@@ -610,17 +542,16 @@ class _LinearGroup(Function):
                 dxs[0] = dxb.sum(0)
             else:
                 dxs = [dxb[g] for g in range(G)]
-        slot, give = arena_take(ctx.pptr, [N * K] * G)   # the owner's gradient arena, when offered for this pass (pre-zeroed)
+        slot, give = arena.take(ctx.pptr, [N * K] * G)   # the owner's gradient arena, when offered for this pass (pre-zeroed)
         if slot is not None:
             dWs = [v.view(N, K) for v in slot]
         else:
             give = True
             dWb = torch.zeros(G, N, K, dtype=torch.float32, device=dev)
             dWs = [dWb[g] for g in range(G)]
-        if slot is not None and all(_dw_can_defer(gs[g], xs[g], None, N, K) for g in range(G)) and \
-                not any(_param_has_hooks(q) for q in ctx.pptr):
+        if slot is not None and all(arena.can_defer(gs[g], xs[g], None, N, K, ctx.pptr[g:g + 1]) for g in range(G)):
             for g in range(G):
-                _dw_defer(gs[g], xs[g], None, dWs[g], None, N, K, ct)
+                arena.defer(gs[g], xs[g], None, dWs[g], None, N, K, ct)
             return (None, None, None, *dxs, *(dWs if give else [None] * G))   # queued until the pass ends
         wgrad.launch(list(gs), list(xs), None, dWs, None, ct, wgrad.SPLITK_CAP_LAYER)
         return (None, None, None, *dxs, *(dWs if give else [None] * G))
@@ -1038,7 +969,7 @@ class _LinearLNGroup(Function):
         # sums): the parameters' slots of the owner's gradient arena when the decoder's backward offered them for this
         # pass (zeroed by its one launch: no fill here, no pack copy later), else ONE zero-filled buffer of our own
         fuse = wgrad.colsum_fusable(list(dlin), xs, None, N, K, ct)
-        slot, give = arena_take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
+        slot, give = arena.take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
         if slot is not None:
             dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
             dWs = [w.view(N, K) for w in dWs]
@@ -1080,183 +1011,6 @@ def linear_ln_group(xs, Ws, bs, gammas, betas, *, ct: int, eps: float = 1e-5):
     G = len(xs)
     need_dx = any(x.requires_grad for x in xs)
     return _LinearLNGroup.apply(ct, float(eps), G, need_dx, *xs, *Ws, *bs, *gammas, *betas)
-
-
-# ---- gradient arena offered for one backward pass ----------------------------------------------------------------------
-# The fused decoder's backward zero-fills the owner's flat gradient buffers with its one zero launch and then OFFERS the
-# slots of the parameters outside the decoder (the input encoders) to the backward functions that run after it in the same
-# pass: they accumulate straight into the slots (no zero-fill launch of their own, no pack copy afterwards) and hand
-# autograd views of them.  The offer ends with the pass (engine callback), so a later backward that does not start with
-# the decoder never sees stale zeroing.  mode "fresh": slots were just zeroed, return the views (autograd adopts them);
-# "accumulate": .grad already aliases the slots (second micro-batch), add in place and return None.
-# Process-global state (the autograd engine runs the backward functions on its own thread, so thread-local would not reach
-# them): ONE backward pass at a time may use an arena -- two models stepping concurrently from different threads must not
-# both be given one.
-class _ArenaState:
-    """The gradient arena of the backward pass in flight, as ONE object with three transitions -- begin() (a whole-pass
-    grad_arena context or the decoder's offer), end() (the pass is over: everything per-pass is dropped) and the accessors
-    below -- instead of loose class attributes that every call site had to clear by hand."""
-
-    def __init__(self):
-        self.zeroed_ptrs = set()   # flat buffers the last fresh pass zero-filled (read by the gradient pack that follows it)
-        self.end()
-
-    def begin(self, mode, by_ptr, whole_pass, pending=None):
-        self.mode = mode                 # None | "fresh" | "accumulate"
-        self.by_ptr = by_ptr             # parameter data_ptr -> (parameter, flat buffer, element offset, numel) of its slot
-        self.written = set()             # slots some function of this pass already returned (a second use adds in place)
-        self.whole_pass = whole_pass     # offered by grad_arena() around the whole backward (the decoder then neither zeroes nor offers)
-        self.pending = pending           # fresh whole-pass arena: buffers still to be zeroed -- by the FIRST consumer
-
-    def end(self, keep_zeroed: bool = True):
-        self.mode, self.by_ptr, self.written, self.whole_pass, self.pending = None, {}, set(), False, None
-        self.multi = set()               # slots that took an in-place second use in a FRESH pass: verified when the pass ends
-        if not keep_zeroed:
-            self.zeroed_ptrs = set()
-
-
-_Arena = _ArenaState()
-
-
-def arena_flush_zero(extra=()) -> bool:
-    """Zero the whole-pass arena's buffers if that is still pending (one launch, ``extra`` buffers of the caller included);
-    False when there was nothing pending (the caller zeroes its own buffers itself)."""
-    if _Arena.pending is None:
-        return False
-    bufs, _Arena.pending = _Arena.pending, None
-    zero_many(list(bufs) + [t for t in extra if t is not None])
-    _Arena.zeroed_ptrs = {b.data_ptr() for b in bufs}
-    return True
-
-
-def arena_zeroed_buffers(consume: bool = True) -> set:
-    """data_ptrs of the flat buffers the last fresh whole-pass arena zero-filled: the gradient pack right after that pass need
-    not zero the slots of parameters that received no gradient.  consume: forget them (one pack per pass)."""
-    z = _Arena.zeroed_ptrs
-    if consume:
-        _Arena.zeroed_ptrs = set()
-    return z
-
-
-def arena_verify(returned=None) -> None:
-    """A fresh pass hands the FIRST arena-aware use of a parameter a view of its slot and lets later arena-aware uses (a tied
-    weight) add into the slot in place.  That is only correct while autograd keeps that view as the gradient: a gradient
-    for the same parameter from a function that is NOT arena-aware makes autograd sum out of place, .grad becomes a tensor
-    of its own and the later in-place additions are lost.  Autograd gives no guarantee here, so the hand-out is CHECKED
-    when the pass ends: every slot that took an in-place second use must still be what .grad aliases.  ``returned``:
-    {parameter data_ptr: gradient torch.autograd.grad() returned} for callers that do not go through .backward()
-    (GraphedQuery3D): checked instead of .grad."""
-    bad = []
-    for q in _Arena.multi:
-        ent = _Arena.by_ptr.get(q)
-        if ent is None:
-            continue
-        p_, fl_, o_, _n = ent
-        g_ = returned.get(q, None) if returned is not None else p_.grad
-        if returned is None and g_ is None:
-            continue      # torch.autograd.grad(): .grad is not written -- the caller verifies what it got back (returned=...)
-        if g_ is None or g_.data_ptr() != fl_.data_ptr() + 4 * o_:
-            bad.append(tuple(p_.shape))
-    _Arena.multi = set()
-    if bad:
-        raise RuntimeError(f"gradient arena: {len(bad)} parameter(s) (shapes {bad[:4]}) received gradients both in place "
-                           "through their arena slot (a tied weight's second use) and through a function that does not use "
-                           "the arena; autograd summed them out of place and the in-place part is lost -- run this backward "
-                           "without ops.grad_arena / enc.grad_arena, or route every use of the parameter through pq3d_amd.ops")
-
-
-class grad_arena:
-    """``with ops.grad_arena(slots, buffers): loss.backward()`` -- the owner of the flat gradient buffers (a
-    FlatGradAllReducer / TrainStep) offers every parameter's slot for the WHOLE backward pass: one zero launch up front
-    (none when every .grad still aliases its slot: accumulation over micro-batches), then every arena-aware backward function
-    -- the heads that run BEFORE the decoder's backward (the caption body), the decoder, the input encoders after it --
-    accumulates in place.  Without this context the decoder's backward makes the offer itself (arena_offer), which only
-    reaches the functions that run after it.
-
-    .grad IS NOT FINAL UNTIL THE CONTEXT EXITS: weight gradients of arena-aware linear layers are queued (_DW_QUEUE) and
-    launched grouped at __exit__ (earlier only at the fused decoder's readiness reports, FlatGradAllReducer.launch() /
-    pack(), or when the queue exceeds _DW_QUEUE_CAP); a reader of p.grad inside the pass sees zeros or partial sums.
-    Parameters with gradient hooks registered are excluded from the deferral for that reason."""
-
-    def __init__(self, slots, buffers, pack_follows: bool = False):
-        # pack_follows: the owner calls FlatGradAllReducer.pack() on these buffers right after the pass; only then is the
-        # "already zero-filled" note (arena_zeroed_buffers) kept past the end of the context
-        self.slots, self.buffers, self.pack_follows = slots, list(buffers), pack_follows
-
-    def verify_returned(self, params, grads) -> None:
-        """For torch.autograd.grad() callers, after the context: the gradients returned for tied parameters that took an
-        in-place second use must alias their slots."""
-        _Arena.multi, _Arena.by_ptr = set(self.multi), dict(self.by_ptr)
-        try:
-            arena_verify({p.data_ptr(): g for p, g in zip(params, grads)})
-        finally:
-            _Arena.end()
-
-    def __enter__(self):
-        _Arena.zeroed_ptrs, _Arena.multi = set(), set()
-        zeroed = {b.data_ptr() for b in self.buffers}
-        ents = {}
-        for i_, q_ in getattr(self.slots, "params", {}).items():
-            fl_, o_, n_ = self.slots[i_]
-            if q_.requires_grad and fl_.data_ptr() in zeroed:
-                ents[q_.data_ptr()] = (q_, fl_, o_, n_)
-        alias = [q_.grad is not None and q_.grad.data_ptr() == f_.data_ptr() + 4 * o_ for q_, f_, o_, n_ in ents.values()]
-        # a later micro-batch of an accumulating step: the in-place gradients of the previous one are still adopted as .grad
-        # (functions only add into slots whose .grad aliases them; gradients that live in tensors of their own keep
-        # accumulating through autograd and are packed afterwards).  No aliasing .grad anywhere: a fresh step, one zero launch
-        mode = "accumulate" if any(alias) else "fresh"
-        # fresh: the buffers are zeroed by the first consumer of the pass (with its own scratch: one launch)
-        _Arena.begin(mode, ents, True, pending=list(self.buffers) if mode == "fresh" else None)
-        return self
-
-    def __exit__(self, *exc):
-        self.multi, self.by_ptr = set(_Arena.multi), dict(_Arena.by_ptr)
-        try:
-            dw_deferred_flush(run=exc[0] is None)   # the queued weight-gradient products of the pass: a few grouped launches
-            if exc[0] is None:
-                arena_flush_zero()    # nobody consumed it: the owner still expects zeroed buffers
-                arena_verify()
-        finally:
-            _Arena.end(keep_zeroed=self.pack_follows)
-        return False
-
-
-def arena_offer(views_by_ptr, mode):
-    _Arena.begin(mode, views_by_ptr, False)
-
-    def _end():
-        if not _Arena.whole_pass:
-            try:
-                arena_verify()
-            finally:
-                _Arena.end()
-    torch.autograd.Variable._execution_engine.queue_callback(_end)
-
-
-def arena_take(ptrs, numels=None):
-    """Slot views for the parameters at ``ptrs`` (all of them or None) and whether to return them to autograd.  ``numels``:
-    the element counts the caller is about to write -- a tensor that only STARTS where a parameter starts (the q rows of a
-    stacked in_proj_weight passed as a slice) is not that parameter."""
-    if _Arena.mode is None or any(q not in _Arena.by_ptr for q in ptrs):
-        return None, False
-    if numels is not None and any(_Arena.by_ptr[q][3] != n for q, n in zip(ptrs, numels)):
-        return None, False
-    arena_flush_zero()
-    # fresh view objects per call: AccumulateGrad adopts a gradient without a copy only when nobody else references it
-    ent = [(p, fl[o:o + n].view(p.shape)) for p, fl, o, n in (_Arena.by_ptr[q] for q in ptrs)]
-    if _Arena.mode == "fresh":
-        seen = [q in _Arena.written for q in ptrs]
-        if any(seen) and not all(seen):
-            return None, False
-        give = not any(seen)
-        if not give:
-            _Arena.multi.update(ptrs)
-    else:   # accumulate: only slots autograd already holds as .grad (anything else still has last step's data in it)
-        if not all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in ent):
-            return None, False
-        give = False
-    _Arena.written.update(ptrs)
-    return [v for _, v in ent], give
 
 
 class _SplitRows(Function):
@@ -1317,7 +1071,7 @@ class _RMSNorm(Function):
         dy = dy.contiguous().float()
         dres = dres.contiguous().float() if dres is not None else None
         dx = torch.empty_like(x)
-        slot, give = arena_take([ctx.pptr], [w.numel()])   # the owner's gradient arena, when offered for this pass (pre-zeroed)
+        slot, give = arena.take([ctx.pptr], [w.numel()])   # the owner's gradient arena, when offered for this pass (pre-zeroed)
         dw = slot[0] if slot is not None else torch.empty_like(w)
         gd = ctx.grad_drop
         dxm, dc = None, None
@@ -1360,7 +1114,7 @@ class _Embedding(Function):
     @staticmethod
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
-        slot, give = arena_take([ctx.pptr], [ctx.shape[0] * ctx.shape[1]])
+        slot, give = arena.take([ctx.pptr], [ctx.shape[0] * ctx.shape[1]])
         dt = slot[0].view(ctx.shape) if slot is not None else torch.zeros(ctx.shape, dtype=torch.float32, device=dout.device)
         dout = dout.contiguous().float()
         if ctx.drop is not None:
@@ -1405,7 +1159,7 @@ class _T5Prep(Function):
         B, T, H, NB = ctx.cfg
         if dbias is None:
             return (None,) * 7
-        slot, give = arena_take([ctx.pptr], [NB * H])
+        slot, give = arena.take([ctx.pptr], [NB * H])
         drel = slot[0].view(NB, H) if slot is not None else _empty(NB, H, dtype=torch.float32, device=dbias.device)
         dbias = dbias.contiguous().float()
         L.call("pq3d_t5_bias_bwd", dbias, buckets, drel, B, T, H, NB, 1 if slot is not None else 0)

@@ -13,15 +13,8 @@ from typing import Iterable, List
 import torch
 import torch.distributed as dist
 
-
-class GradSlots(dict):
-    """{id(param): (flat buffer, element offset, numel)} plus ``params`` = {id(param): param}: the slot map handed to the
-    fused executor (``encoder.grad_arena``).  ``params`` lets the executor offer the slots of parameters OUTSIDE the decoder
-    (the input encoders) to their own backward functions for the duration of one backward pass (ops.arena_*)."""
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.params = {}
+from . import arena
+from .arena import GradSlots
 
 
 class NativeComm:
@@ -125,6 +118,7 @@ class FlatGradAllReducer:
                 size += nb
         self.buckets = [b for b in self.buckets if b]
         self.flat = [torch.zeros(sum(p.numel() for p in b), dtype=torch.float32, device=b[0].device) for b in self.buckets]
+        self._slots = self.slots()   # pack() / unpack_views() look the slots up here
         self._side = None        # side stream of the early launches
         self._pending = []       # (work handle or None, bucket index)
         self._launched = set()
@@ -152,9 +146,9 @@ class FlatGradAllReducer:
         unused = []   # slots of parameters without a gradient this step: zeroed by ONE launch at the end
         prezeroed = set()
         if self.flat and self.flat[0].is_cuda:
-            from . import ops
-            ops.dw_deferred_flush()   # no reader of the slots gets ahead of queued weight-gradient products
-            prezeroed = ops.arena_zeroed_buffers()   # buffers a whole-pass gradient arena zero-filled for this very pass
+            arena.dw_deferred_flush()   # no reader of the slots gets ahead of queued weight-gradient products
+            prezeroed = arena.zeroed_buffers()   # buffers a whole-pass gradient arena zero-filled for this very pass
+        slots = self._slots
         for bi, (flat, bucket) in enumerate(zip(self.flat, self.buckets)):
             if buckets is not None and bi not in buckets:
                 continue
@@ -162,31 +156,22 @@ class FlatGradAllReducer:
                 # its all-reduce is already in flight on the side stream (early launch from inside the backward: the
                 # gradients were written in place): packing now would race with / overwrite the reduced data
                 continue
-            views, grads, off = [], [], 0
+            views, grads = [], []
             for p in bucket:
-                n = p.numel()
-                v = flat[off:off + n].view_as(p)
-                if p.grad is not None:
-                    if p.grad.data_ptr() != v.data_ptr():
-                        views.append(v)
-                        grads.append(p.grad)
-                elif flat.data_ptr() not in prezeroed:
-                    unused.append(v)
-                off += n
+                if p.grad is None:
+                    if flat.data_ptr() not in prezeroed:
+                        unused.append(slots.view(p))
+                elif not slots.aliased(p):
+                    views.append(slots.view(p))
+                    grads.append(p.grad)
             if views:
                 if flat.is_cuda and all(g.dtype == torch.float32 for g in grads):
                     from . import ops           # one launch of our own (torch's multi-tensor copy: 11 us for 60 small tensors)
                     ops.copy_many(views, grads)
                 else:
                     torch._foreach_copy_(views, grads)
-        if unused:
-            if unused[0].is_cuda:
-                from . import ops           # (an unused sub-module -- the caption model's encoder stack -- is 50 slots)
-                for s0 in range(0, len(unused), 64):
-                    ops.zero_many(unused[s0:s0 + 64])
-            else:
-                for v in unused:
-                    v.zero_()
+        for s0 in range(0, len(unused), 64):   # (an unused sub-module -- the caption model's encoder stack -- is 50 slots)
+            arena.zero(unused[s0:s0 + 64])
 
     # ---- collective -------------------------------------------------------------------------------------------------
     def _world(self) -> int:
@@ -253,8 +238,7 @@ class FlatGradAllReducer:
         if not self._active() or bi in self._launched:
             return
         if self.flat[bi].is_cuda:
-            from . import ops
-            ops.dw_deferred_flush()   # weight gradients still queued for this pass land before the bucket leaves
+            arena.dw_deferred_flush()   # weight gradients still queued for this pass land before the bucket leaves
         cur = torch.cuda.current_stream() if self.flat[bi].is_cuda else None
         if cur is not None and torch.cuda.is_current_stream_capturing():
             # Inside a HIP-graph capture the collective stays ON the capturing stream (a synchronous op: RCCL's internal
@@ -320,12 +304,8 @@ class FlatGradAllReducer:
 
     def unpack_views(self) -> None:
         """Point every .grad at its slice of the reduced flat buffer."""
-        for flat, bucket in zip(self.flat, self.buckets):
-            off = 0
-            for p in bucket:
-                n = p.numel()
-                p.grad = flat[off:off + n].view_as(p)
-                off += n
+        for p in self.params:
+            p.grad = self._slots.view(p)
 
     def step(self) -> None:
         self.pack()

@@ -21,7 +21,7 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 
 from . import _lib as L
-from . import ops
+from . import arena, ops
 from .parallel import FlatGradAllReducer
 
 
@@ -124,7 +124,7 @@ class TrainStep:
             loss = loss * loss_scale
         enc = getattr(self.model, "unified_encoder", None)
         if enc is not None and getattr(enc, "grad_arena", None) is not None:
-            with ops.grad_arena(enc.grad_arena, enc.grad_arena_buffers, pack_follows=True):   # every slot offered for the whole pass
+            with arena.grad_arena(enc.grad_arena, enc.grad_arena_buffers, pack_follows=True):   # every slot offered for the whole pass
                 loss.backward()
         else:
             loss.backward()

@@ -230,7 +230,7 @@ def test_encoder_gradients_written_into_the_offered_arena_slots():
     enc.grad_arena, enc.grad_arena_buffers = slots, list(red.flat)
     model.zero_grad(set_to_none=True)
     loss_of(model(dict(dda))).backward()
-    assert ops._Arena.mode is None   # the offer ended with the backward pass
+    assert not ops.arena.active()   # the offer ended with the backward pass
     in_place = [n for n, p in model.named_parameters() if id(p) not in dec and p.grad is not None
                 and p.grad.data_ptr() == slots[id(p)][0][slots[id(p)][1]:].data_ptr()]
     assert in_place, "no encoder gradient was written in place"
@@ -325,7 +325,7 @@ def test_whole_pass_gradient_arena_with_modular_functions():
         p.grad = None
     with ops.grad_arena(slots, red.flat):
         loss_of().backward()
-    assert ops._Arena.mode is None and ops._Arena.pending is None
+    assert not ops.arena.active() and not ops.arena.zero_pending()
     in_place = [p.grad.data_ptr() == slots[id(p)][0].data_ptr() + 4 * slots[id(p)][1] for p in params]
     assert in_place[:6] == [True] * 6 and not in_place[6], in_place
     for a, b in zip(grads(), ref1):

@@ -937,12 +937,16 @@ int pq3d_adamw(float* p, const float* g, float* m, float* v, int64_t n, const pq
  * losses of SetCriterion (criterion.py:136-206).  Per prediction layer, with X = mask logits [B, Ns, Nq] (segments
  * first), T = padded target masks [B, Nt, Ns] (0/1 floats), seg_len[b] = segments of scene b (matcher.py:139-148 uses
  * the first tgt_mask.shape[1] columns), n_inst[b] = targets of scene b:
- *   pq3d_mask_cost_prep : sig = sigma(X) (0 past seg_len), partial column sums of softplus(X) and sigma(X)
- *                         ([B, nsplit, Nq], nsplit = pq3d_mask_cost_nsplit(Ns))
- *   pq3d_gemm (ct F32, groups 2, batch B, A = T, B = X | sig with transB): TX = T X, TS = T sigma(X)   [B, Nt, Nq]
- *   pq3d_match_cost     : cost_mask = (sum_s softplus(x) - TX)/S  (== batch_sigmoid_ce_loss: pos - neg = -x),
- *                         cost_dice = 1 - (2 TS + 1)/(sum sigma + sum T + 1), cost_class = -softmax(cls)[label]
- *                         (-1 for ignore_label), cost = w_mask cm + w_class cc + w_dice cd     [B, Nq, Nt]
+ *   pq3d_mask_cost_prep : sig = [sigma(-X) ; sigma(X)], rel = [relu(-X) ; relu(X)] (all 0 past seg_len), partial column sums
+ *                         of l(X) = log1p(exp(-|X|)) and sigma(X) ([B, nsplit, Nq], nsplit = pq3d_mask_cost_nsplit(Ns))
+ *   pq3d_gemm (ct F32, groups 2, batch B, transB, K = 2 Ns): TR = [T | 1 - T] rel, ND = [T | 1 - T] sig   [B, Nt, Nq]
+ *   pq3d_match_cost     : cost_mask = (TR + sum_s l(x))/S  (== batch_sigmoid_ce_loss: softplus(-+x) = relu(-+x) + l(x);
+ *                         every term is non-negative, so a small entry keeps its digits -- the shorter
+ *                         (sum_s softplus(x) - T X)/S cancels them away at confident, correct masks),
+ *                         cost_dice = ND/(sum sigma + sum T + 1)  (== 1 - (2 T sigma + 1)/(sum sigma + sum T + 1), again
+ *                         without the cancellation), cost_class = -softmax(cls)[label]
+ *                         (-1 for ignore_label, NaN for any other label outside [0, C)),
+ *                         cost = w_mask cm + w_class cc + w_dice cd     [B, Nq, Nt]
  *   (host)              : scipy.optimize.linear_sum_assignment per scene, as the reference
  *   losses              : sigmoid_ce_loss / dice_loss of a matched pair (criterion.py:27-70) ARE cost_mask / cost_dice at
  *                         that pair -> gathers; pq3d_matched_mask_grad writes d loss / d X (zero off the matched columns);
@@ -956,15 +960,16 @@ typedef struct {
   int32_t layers, B, Ns, Nq, nsplit;
   const float* X[PQ3D_MAX_GROUPS];   /* mask logits [B, Ns, Nq] of each layer */
   const int32_t* seg_len;            /* [B] */
-  float* sig;                        /* [layers, B, Ns, Nq] */
-  float* sp_part;                    /* [layers, B, nsplit, Nq] */
-  float* sg_part;                    /* [layers, B, nsplit, Nq] */
+  float* sig;                        /* [layers, B, 2 Ns, Nq]: rows s < Ns sigma(-x), rows Ns + s sigma(x) */
+  float* sp_part;                    /* [layers, B, nsplit, Nq]: partial sums of log1p(exp(-|x|)) */
+  float* sg_part;                    /* [layers, B, nsplit, Nq]: partial sums of sigma(x) */
+  float* rel;                        /* [layers, B, 2 Ns, Nq]: rows s < Ns relu(-x), rows Ns + s relu(x) */
 } pq3d_mask_prep_desc;
 typedef struct {
   int32_t layers, B, Nq, Nt, Ns, C, nsplit;
   float w_class, w_mask, w_dice;
   int64_t ignore_label;
-  const float* TXS;         /* [layers, 2, B, Nt, Nq]: T X and T sigma(X) (pq3d_gemm outputs) */
+  const float* TXS;         /* [layers, 2, B, Nt, Nq]: [T | 1 - T] rel and [T | 1 - T] sig (pq3d_gemm outputs) */
   const float* sp_part;     /* [layers, B, nsplit, Nq] */
   const float* sg_part;     /* [layers, B, nsplit, Nq] */
   const float* t_sum;       /* [B, Nt] = sum_s T */
@@ -976,7 +981,7 @@ typedef struct {
 } pq3d_match_cost_desc;
 typedef struct {
   int32_t layers, B, Ns, Nq, Nt, Nm;   /* Nm = row length of q_idx / t_idx */
-  const float* sig;            /* [layers, B, Ns, Nq] from pq3d_mask_cost_prep */
+  const float* sig;            /* [layers, B, 2 Ns, Nq] from pq3d_mask_cost_prep */
   const float* T;              /* [B, Nt, Ns] */
   const float* TXS;            /* [layers, 2, B, Nt, Nq] */
   const float* sig_sum;        /* [layers, B, Nq] (sg_part summed over splits) */

@@ -69,7 +69,7 @@ SUMSQ_PARTIALS = 1024
 class MaskPrepDesc(C.Structure):
     _fields_ = [("layers", C.c_int32), ("B", C.c_int32), ("Ns", C.c_int32), ("Nq", C.c_int32), ("nsplit", C.c_int32),
                 ("X", C.c_void_p * MAXG), ("seg_len", C.c_void_p), ("sig", C.c_void_p), ("sp_part", C.c_void_p),
-                ("sg_part", C.c_void_p)]
+                ("sg_part", C.c_void_p), ("rel", C.c_void_p)]
 
 
 class MatchCostDesc(C.Structure):

@@ -2,9 +2,16 @@
 // HungarianMatcher.memory_efficient_forward (modules/third_party/mask3d/matcher.py:104-184) and the matched losses of
 // SetCriterion (criterion.py:136-206), re-derived so that ONE grouped fp32 MFMA GEMM per prediction layer carries all
 // the segment-dimension work:
-//     pos - neg = softplus(-x) - softplus(x) = -x   =>
-//     cost_mask[q,t] = ( sum_s softplus(x_sq) - (T X)[t,q] ) / S            (batch_sigmoid_ce_loss, matcher.py:37-60)
-//     cost_dice[q,t] = 1 - (2 (T sigma(X))[t,q] + 1) / (sum_s sigma(x_sq) + sum_s T_ts + 1)      (matcher.py:12-28)
+//     pos = softplus(-x) = relu(-x) + l(x),  neg = softplus(x) = relu(x) + l(x),  l(x) = log1p(exp(-|x|))   =>
+//     cost_mask[q,t] = ( (T relu(-X))[t,q] + ((1 - T) relu(X))[t,q] + sum_s l(x_sq) ) / S     (batch_sigmoid_ce_loss,
+//                                                                                            matcher.py:37-60)
+// as ONE product over a doubled contraction, [T | 1 - T] [relu(-X) ; relu(X)].  Every term is non-negative, so an entry keeps
+// fp32 RELATIVE accuracy however small it is.  (The shorter pos - neg = -x  =>  (sum_s softplus(x) - T X) / S is a difference of
+// two O(|x| S) sums: at confident, correct masks the matched entry -- the reported loss_mask -- lost every digit.)
+//     cost_dice[q,t] = 1 - (2 I + 1) / D = ( (T sigma(-X))[t,q] + ((1 - T) sigma(X))[t,q] ) / D,   I = (T sigma(X))[t,q],
+//                      D = sum_s sigma(x_sq) + sum_s T_ts + 1                                      (matcher.py:12-28)
+// over the same doubled contraction, [T | 1 - T] [sigma(-X) ; sigma(X)]: again non-negative terms only, where 1 - ratio loses
+// the digits of a small dice cost.
 // with X = mask logits [S, Nq] of one scene (segments first, as the mask head writes them), T = target masks [Nt, S].
 // With num_points = -1 (all points, the shipped config) the matched losses sigmoid_ce_loss / dice_loss
 // (criterion.py:27-70) are exactly the matched ENTRIES of those two matrices, so the forward losses are gathers and
@@ -17,16 +24,20 @@ namespace {
 constexpr int PREP_ROWS = 256;   // segments per block of the prep kernel
 constexpr int GRAD_ROWS = 16;    // segments per block of the gradient kernel (LDS tile 2 x 16 x (Nq+1) floats)
 
-PQ_DEV float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 PQ_DEV float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+// BCE with logits, softplus(x) - x t, with the two O(|x|) parts cancelled BEFORE the O(exp(-|x|)) part is added: at a confident
+// correct logit (x = 12, t = 1) fp32 softplus(x) - x * t keeps one digit of the 6e-6 that is the term, this keeps all of them
+PQ_DEV float bce_f(float x, float t) { return (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x))); }
 
-// sig[b,s,q] = sigma(x) (0 for s >= len_b); partial column sums over this block's rows of softplus(x) and sigma(x)
+// sig[b,s,q] = sigma(-x), sig[b,Ns+s,q] = sigma(x), rel[b,s,q] = relu(-x), rel[b,Ns+s,q] = relu(x) (all 0 for s >= len_b);
+// partial column sums over this block's rows of l(x) = log1p(exp(-|x|)) and sigma(x)
 __global__ __launch_bounds__(256) void mask_cost_prep_kernel(const pq3d_mask_prep_desc d) {
   __shared__ float red[2][4][64];
   const int Ns = d.Ns, Nq = d.Nq, nsplit = d.nsplit;
   const int layer = blockIdx.z / d.B, bb = blockIdx.z % d.B;
   const float* __restrict__ X = d.X[layer];
-  float* __restrict__ sig = d.sig + (long)layer * d.B * Ns * Nq;
+  float* __restrict__ sig = d.sig + (long)layer * d.B * 2 * Ns * Nq;
+  float* __restrict__ rel = d.rel + (long)layer * d.B * 2 * Ns * Nq;
   float* __restrict__ sp_part = d.sp_part + (long)layer * d.B * nsplit * Nq;
   float* __restrict__ sg_part = d.sg_part + (long)layer * d.B * nsplit * Nq;
   const int b = bb, split = blockIdx.y, q = blockIdx.x * 64 + (threadIdx.x & 63), rg = threadIdx.x >> 6;
@@ -39,9 +50,13 @@ __global__ __launch_bounds__(256) void mask_cost_prep_kernel(const pq3d_mask_pre
       const float x = X[i];
       const bool in = s < len;
       const float g = in ? sigmoid_f(x) : 0.f;
-      sig[i] = g;
+      const long ir = ((long)b * 2 * Ns + s) * Nq + q;
+      sig[ir] = in ? sigmoid_f(-x) : 0.f;
+      sig[ir + (long)Ns * Nq] = g;
+      rel[ir] = in ? fmaxf(-x, 0.f) : 0.f;
+      rel[ir + (long)Ns * Nq] = in ? fmaxf(x, 0.f) : 0.f;
       sg += g;
-      sp += in ? softplus_f(x) : 0.f;
+      sp += in ? log1pf(expf(-fabsf(x))) : 0.f;
     }
   }
   red[0][rg][threadIdx.x & 63] = sp;
@@ -94,17 +109,22 @@ __global__ __launch_bounds__(64) void match_cost_kernel(const pq3d_match_cost_de
     const long o = ((long)b * d.Nq + q) * d.Nt + t;
     if (t >= nt) { d.cost[o] = 0.f; d.cost_mask[o] = 0.f; d.cost_dice[o] = 0.f; continue; }
     const long gi = ((long)b * d.Nt + t) * d.Nq + q;
-    const float cm = (sp - d.TX[gi]) * inv_s;
-    const float cd = 1.f - (2.f * d.TS[gi] + 1.f) / (sg + d.t_sum[(long)b * d.Nt + t] + 1.f);
+    const float cm = (d.TX[gi] + sp) * inv_s;
+    const float cd = d.TS[gi] / (sg + d.t_sum[(long)b * d.Nt + t] + 1.f);
     const long lab = d.labels[(long)b * d.Nt + t];
-    const float cc = lab == d.ignore_label ? -1.f : -expf(lg[lab] - mx) / se;   // -softmax prob; "perfect match" if ignored
+    // -softmax prob; "perfect match" if ignored; a label outside [0, C) poisons the entry (NaN, as the CE kernels do) instead
+    // of reading out of bounds: host matching then raises scipy's error, device matching reports PQ3D_LSAP_INVALID
+    const float cc = lab == d.ignore_label ? -1.f
+                     : ((unsigned long)lab < (unsigned long)d.C ? -expf(lg[lab] - mx) / se : NAN);
     d.cost_mask[o] = cm;
     d.cost_dice[o] = cd;
     d.cost[o] = d.w_mask * cm + d.w_class * cc + d.w_dice * cd;
   }
 }
 
-// dX[b,s,q_j] = gm_b * (sigma - T)/S_b + gd_b * sigma(1-sigma) * (-(2 T D - (2 TS + 1)) / D^2),  D = sig_sum + t_sum + 1;
+// dX[b,s,q_j] = gm_b * (sigma - T)/S_b + gd_b * sigma(1-sigma) * (D (1 - 2 T) - ND) / D^2,  D = sig_sum + t_sum + 1, ND = the dice
+// numerator product (2 I + 1 = D - ND); sigma - T = (1 - T) sigma(x) - T sigma(-x) and sigma (1 - sigma) = sigma(x) sigma(-x) from
+// the two stored planes, so that a confident correct logit (sigma = 1 - 6e-6) keeps the digits of its small gradient;
 // every other entry of dX is zero.  Block = (16-segment tile, scene, layer): X / dX tiles go through LDS so that both the
 // [S, Nq]-major logits and the [Nt, S]-major targets are read and written coalesced.
 __global__ __launch_bounds__(256) void matched_mask_grad_kernel(const pq3d_mask_grad_desc dd) {
@@ -117,7 +137,7 @@ __global__ __launch_bounds__(256) void matched_mask_grad_kernel(const pq3d_mask_
   } d;
   const int layer = blockIdx.z;
   d.B = dd.B; d.Ns = dd.Ns; d.Nq = dd.Nq; d.Nt = dd.Nt; d.Nm = dd.Nm;
-  d.sig = dd.sig + (long)layer * dd.B * dd.Ns * dd.Nq;
+  d.sig = dd.sig + (long)layer * dd.B * 2 * dd.Ns * dd.Nq;
   d.T = dd.T; d.t_sum = dd.t_sum; d.seg_len = dd.seg_len;
   d.TS = dd.TXS + ((long)layer * 2 + 1) * dd.B * dd.Nt * dd.Nq;
   d.sig_sum = dd.sig_sum + (long)layer * dd.B * dd.Nq;
@@ -133,7 +153,7 @@ __global__ __launch_bounds__(256) void matched_mask_grad_kernel(const pq3d_mask_
   for (int i = tid; i < GRAD_ROWS * d.Nq; i += 256) {
     const int r = i / d.Nq, c = i % d.Nq;
     const int s = s0 + r;
-    sg_t[r * ld + c] = s < d.Ns ? d.sig[((long)b * d.Ns + s) * d.Nq + c] : 0.f;
+    sg_t[r * ld + c] = s < d.Ns ? d.sig[((long)b * 2 * d.Ns + d.Ns + s) * d.Nq + c] : 0.f;
     g_t[r * ld + c] = 0.f;
   }
   __syncthreads();
@@ -143,11 +163,11 @@ __global__ __launch_bounds__(256) void matched_mask_grad_kernel(const pq3d_mask_
   if (s < len) {
     for (int j = tid / GRAD_ROWS; j < nm; j += 256 / GRAD_ROWS) {
       const int q = d.q_idx[(long)b * d.Nm + j], t = d.t_idx[(long)b * d.Nm + j];
-      const float sg = sg_t[sl * ld + q];
+      const float sg = sg_t[sl * ld + q], sn = d.sig[((long)b * 2 * d.Ns + s) * d.Nq + q];   // sigma(x), sigma(-x)
       const float tv = d.T[((long)b * d.Nt + t) * d.Ns + s];
       const float ssum = d.sig_sum[(long)b * d.Nq + q], D = ssum + d.t_sum[(long)b * d.Nt + t] + 1.f;
-      const float num = 2.f * d.TS[((long)b * d.Nt + t) * d.Nq + q] + 1.f;
-      g_t[sl * ld + q] = gm * (sg - tv) + gd * sg * (1.f - sg) * (-(2.f * tv * D - num) / (D * D));
+      const float nd = d.TS[((long)b * d.Nt + t) * d.Nq + q];
+      g_t[sl * ld + q] = gm * ((1.f - tv) * sg - tv * sn) + gd * sg * sn * ((D * (1.f - 2.f * tv) - nd) / (D * D));
     }
   }
   __syncthreads();
@@ -179,7 +199,7 @@ __global__ __launch_bounds__(256) void padded_mask_sums_kernel(const float* __re
       const long ti = ((long)b * N + n) * S + s;
       const float p = P[ti] ? 1.f : 0.f, t = T[ti], x = lds[sl * ld + n];
       const float sg = sigmoid_f(x);
-      v[0] = (softplus_f(x) - x * t) * p;   // BCE with logits = softplus(x) - x t
+      v[0] = bce_f(x, t) * p;
       v[1] = p;
       v[2] = sg * t * p;
       v[3] = (sg + t) * p;
@@ -208,10 +228,11 @@ __global__ __launch_bounds__(256) void padded_mask_grad_kernel(const float* __re
       const long ti = ((long)b * N + n) * S + s;
       float g = 0.f;
       if (P[ti]) {
-        const float t = T[ti], sg = sigmoid_f(lds[sl * ld + n]);
+        const float t = T[ti], sg = sigmoid_f(lds[sl * ld + n]), sn = sigmoid_f(-lds[sl * ld + n]);
         const float* sm = sums + ((long)b * N + n) * 4;
         const float U = sm[3] + 1e-6f, I2 = 2.f * sm[2] + 1e-6f;
-        g = gm[(long)b * N + n] * (sg - t) + gd[(long)b * N + n] * sg * (1.f - sg) * (-(2.f * t * U - I2) / (U * U));
+        // sigma - t and sigma (1 - sigma) from sigma(x) and sigma(-x): no digit lost at a confident correct logit
+        g = gm[(long)b * N + n] * ((1.f - t) * sg - t * sn) + gd[(long)b * N + n] * sg * sn * (-(2.f * t * U - I2) / (U * U));
       }
       lds[sl * ld + n] = g;   // each (row, n) is read and rewritten by the same thread
     }
@@ -373,7 +394,7 @@ extern "C" int pq3d_mask_cost_prep(const pq3d_mask_prep_desc* dp, void* stream) 
   PQ_CHECK_ARG(dp != nullptr, "pq3d_mask_cost_prep: null descriptor");
   const pq3d_mask_prep_desc d = *dp;
   if (int e = check_layers(d.layers, "pq3d_mask_cost_prep: layers must be in [1, PQ3D_MAX_GROUPS]")) return e;
-  PQ_CHECK_ARG(d.seg_len && d.sig && d.sp_part && d.sg_part && d.B >= 0 && d.Ns >= 1 && d.Nq >= 1 &&
+  PQ_CHECK_ARG(d.seg_len && d.sig && d.rel && d.sp_part && d.sg_part && d.B >= 0 && d.Ns >= 1 && d.Nq >= 1 &&
                d.nsplit == (d.Ns + PREP_ROWS - 1) / PREP_ROWS, "pq3d_mask_cost_prep: bad args");
   for (int l = 0; l < d.layers; ++l) PQ_CHECK_ARG(d.X[l] != nullptr, "pq3d_mask_cost_prep: null X");
   if (d.B == 0) return 0;

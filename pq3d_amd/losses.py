@@ -73,27 +73,32 @@ class PaddedTargets:
 
 def _costs(masks, logits, T, labels, seg_len, n_inst_dev, t_sum, w, ignore_label):
     """Cost matrices of ALL prediction layers and scenes in three launches: cost[l] = (total, mask term, dice term)
-    [layers, 3, B, Nq, Nt].  Also returns what the gradient stage needs: sigma(X), (T X | T sigma(X)), sum_s sigma."""
+    [layers, 3, B, Nq, Nt].  Also returns what the gradient stage needs: (sigma(-X) ; sigma(X)), (mask product | dice
+    numerator product), sum_s sigma.  Both terms are sums of non-negative terms over a doubled contraction,
+    [T | 1 - T] [relu(-X) ; relu(X)] + sum_s log1p(exp(-|x|)) and [T | 1 - T] [sigma(-X) ; sigma(X)] / D (see csrc/loss.hip): their
+    matched entries are the reported loss_mask / loss_dice, which are small exactly when the model is good."""
     n_layers = len(masks)
     B, Ns, Nq = masks[0].shape
     Nt, Ccls = T.shape[1], logits[0].shape[-1]
     dev = T.device
     assert n_layers <= L.MAXG // 2, "too many prediction layers for one grouped launch"
     nsplit = L.lib().pq3d_mask_cost_nsplit(Ns)
-    sig = torch.empty(n_layers, B, Ns, Nq, dtype=torch.float32, device=dev)
+    sig = torch.empty(n_layers, B, 2 * Ns, Nq, dtype=torch.float32, device=dev)
+    rel = torch.empty(n_layers, B, 2 * Ns, Nq, dtype=torch.float32, device=dev)
     part = torch.empty(2, n_layers, B, nsplit, Nq, dtype=torch.float32, device=dev)
     p = L.MaskPrepDesc()
     p.layers, p.B, p.Ns, p.Nq, p.nsplit = n_layers, B, Ns, Nq, nsplit
     for l in range(n_layers):
         p.X[l] = L.ptr(masks[l])
-    p.seg_len, p.sig, p.sp_part, p.sg_part = L.ptr(seg_len), L.ptr(sig), L.ptr(part[0]), L.ptr(part[1])
+    p.seg_len, p.sig, p.sp_part, p.sg_part, p.rel = map(L.ptr, (seg_len, sig, part[0], part[1], rel))
     L.call("pq3d_mask_cost_prep", p)
-    # ONE grouped + batched exact-f32 MFMA GEMM: groups = (layer, X | sigma(X)), batch = scenes
+    # ONE grouped + batched exact-f32 MFMA GEMM over K = 2 Ns: groups = (layer, relu planes | sigma planes), batch = scenes
     TXS = torch.empty(n_layers, 2, B, Nt, Nq, dtype=torch.float32, device=dev)
-    Bops = [t for l in range(n_layers) for t in (masks[l], sig[l])]
+    T2 = torch.cat((T, 1.0 - T), 2)
+    Bops = [t for l in range(n_layers) for t in (rel[l], sig[l])]
     Cs = [TXS[l, k] for l in range(n_layers) for k in (0, 1)]
-    L.gemm(M=Nt, N=Nq, K=Ns, A=[T] * (2 * n_layers), B=Bops, Cs=Cs, ct=L.F32, lda=Ns, ldb=Nq, ldc=Nq, transB=True,
-           batch=B, strideA=Nt * Ns, strideB=Ns * Nq, strideC=Nt * Nq)
+    L.gemm(M=Nt, N=Nq, K=2 * Ns, A=[T2] * (2 * n_layers), B=Bops, Cs=Cs, ct=L.F32, lda=2 * Ns, ldb=Nq, ldc=Nq, transB=True,
+           batch=B, strideA=Nt * 2 * Ns, strideB=2 * Ns * Nq, strideC=Nt * Nq)
     cost = torch.empty(n_layers, 3, B, Nq, Nt, dtype=torch.float32, device=dev)
     d = L.MatchCostDesc()
     d.layers, d.B, d.Nq, d.Nt, d.Ns, d.C, d.nsplit = n_layers, B, Nq, Nt, Ns, Ccls, nsplit

@@ -1169,6 +1169,52 @@ int pq3d_attn_causal_fwd(const void* qkv, const uint8_t* valid, void* out, int32
 int pq3d_l2norm_rows(const void* x, void* y, int64_t R, int32_t d, int32_t dt_x, int32_t dt_y, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sparse 3-D convolution, forward (pq3d_amd/csrc/sparse_conv.hip; host side pq3d_amd/sparse.py).  Replaces the
+ * MinkowskiConvolution / MinkowskiConvolutionTranspose + MinkowskiBatchNorm (eval) + residual add + MinkowskiReLU sequences
+ * of the voxel backbone (modules/third_party/mask3d/res16unet.py:241-314, resnet_block.py:52-68), one launch per convolution:
+ *     out[o, col_off + n] = act( (sum_k sum_c x[nbr[o, k], c] * W[k, c, n]) * scale[n] + shift[n] + bias[n] + residual[o, n] )
+ * A term with nbr[o, k] < 0 (or >= N_in: never dereferenced) is absent.  x [N_in, ldx] fp32; nbr [N_out, K] int32 (the
+ * kernel map: row of x under offset k of output row o); W [K, Cin, Cout] of dtype dtW (fp32, or bf16 converted once for a
+ * frozen network); scale / shift / bias [Cout] fp32, each optional (NULL); residual [N_out, ldr] fp32, optional; out
+ * [N_out, ldo] fp32, written at columns [col_off, col_off + Cout) only -- a transposed convolution writes the left columns
+ * of the buffer the next block reads as the concatenation with its skip connection.  act: PQ3D_ACT_NONE / PQ3D_ACT_RELU.
+ * ct: PQ3D_F32 (exact-f32 MFMA) or PQ3D_BF16 (both operands rounded to bf16, fp32 accumulation).
+ * Output-stationary: a workgroup owns PQ3D_SPARSE_TILE consecutive output rows x a tile of output channels, loops over the
+ * offsets, gathers the neighbour rows into LDS, accumulates on MFMA in registers and stores every element once.  No atomics:
+ * results are bitwise reproducible and do not depend on the tiling.  occ (optional): [ceil(N_out / PQ3D_SPARSE_TILE), 4]
+ * uint32 words, bit k set iff some row of the tile has offset k present (pq3d_sparse_nbr builds it; K <= 128): offsets whose
+ * bit is clear are skipped.  Cin < 16 with K > 1 (the 5^3 stem on 3 input channels) contracts over the packed (offset,
+ * channel) index instead of padding every offset to an MFMA k-step; with ct = PQ3D_BF16 that path keeps x exact (two bf16
+ * planes, hi + lo) and rounds only W to bf16.
+ *
+ * pq3d_sparse_nbr: kernel map + occupancy words of one (level, kernel) pair.  keys [n_in] int64, ascending and distinct:
+ * key = b << 60 | (z + 2^19) << 40 | (y + 2^19) << 20 | (x + 2^19) of the INPUT level's voxels in units of its tensor stride
+ * (row r of x is the voxel of keys[r]); q [n_out, 4] int32 (b, x, y, z) the OUTPUT voxels in the same units; offs [K, 3]
+ * int32 (dx, dy, dz) the offsets: nbr[o, k] = row of the voxel at q[o] + offs[k] in the same batch item, or -1 (binary
+ * search; a neighbour outside the 20-bit coordinate range is absent).  keys == NULL: nbr is taken as given (the stride-2
+ * tables are written by the host side) and only occ is computed.  occ may be NULL.
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_SPARSE_TILE 64
+typedef struct {
+  int32_t N_out, N_in, Cin, Cout, K;
+  int32_t ct, dtW, act, col_off;
+  int32_t ntl; /* output channels per workgroup / 16: 2, 4, 6 or 8; 0 = chosen from the sizes.  Changes no output bit. */
+  int64_t ldx, ldo, ldr;
+  const float* x;
+  const int32_t* nbr;
+  const void* W;
+  const float* scale;
+  const float* shift;
+  const float* bias;
+  const float* residual;
+  float* out;
+  const uint32_t* occ;
+} pq3d_sparse_conv_desc;
+int pq3d_sparse_conv_fwd(const pq3d_sparse_conv_desc* d, void* stream);
+int pq3d_sparse_nbr(const int64_t* keys, int64_t n_in, const int32_t* q, int64_t n_out, const int32_t* offs, int32_t K,
+                    int32_t* nbr, uint32_t* occ, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange over RCCL / xGMI (SURVEY 8b's export list: pq3d_comm_init, pq3d_allreduce_grads; 8e).
  * Replaces, for a host that does not go through torch.distributed: DistributedDataParallel's bucketed all-reduce(mean) of
  * the parameter gradients every step (reference trainer/build.py:66-75 via accelerate; the only collective on the path).

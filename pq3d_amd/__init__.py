@@ -10,4 +10,7 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
     if name == "CLIPLanguageEncoder":
         from .clip_text import CLIPLanguageEncoder
         return CLIPLanguageEncoder
+    if name == "Res16UNet34C":
+        from .sparse import Res16UNet34C
+        return Res16UNet34C
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -208,6 +208,13 @@ class ChainSaBwdDesc(C.Structure):
                 ("Wo", C.c_void_p * 3), ("do_all", C.c_void_p * 3), ("flags", C.c_void_p), ("err", C.c_void_p), ("lnws", C.c_void_p)]
 
 
+class SparseConvDesc(C.Structure):
+    """pq3d_sparse_conv_desc (csrc/sparse_conv.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("N_out", "N_in", "Cin", "Cout", "K", "ct", "dtW", "act", "col_off", "ntl")] + \
+               [(n, C.c_int64) for n in ("ldx", "ldo", "ldr")] + \
+               [(n, C.c_void_p) for n in ("x", "nbr", "W", "scale", "shift", "bias", "residual", "out", "occ")]
+
+
 _lib = None
 
 _SIGS = {
@@ -358,6 +365,9 @@ _SIGS = {
                         C.c_int32, C.c_void_p],
     "pq3d_attn_causal_fwd": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p],
     "pq3d_l2norm_rows": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p],
+    # sparse 3-D convolution + kernel maps of the voxel backbone (csrc/sparse_conv.hip)
+    "pq3d_sparse_conv_fwd": [C.POINTER(SparseConvDesc), C.c_void_p],
+    "pq3d_sparse_nbr": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     # data-parallel gradient exchange over RCCL (csrc/comm.hip)
     "pq3d_comm_unique_id": [C.c_void_p],
     "pq3d_comm_init": [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],

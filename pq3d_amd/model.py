@@ -94,8 +94,8 @@ class Query3DUnified(nn.Module):
                     self.txt_encoder = build_module_by_name(cfg.model.get("txt_encoder"))
                 continue
             # voxel without use_offline_voxel_fts: the reference runs its MinkowskiEngine backbone inside the model
-            # (query3d_unified.py:146-152); here the backbone is outside (out of scope) and the voxel encoder is the
-            # post-backbone part (M.PCDMask3DSegLevelEncoder) fed the backbone's per-level features
+            # (query3d_unified.py:146-152); here the voxel encoder (M.PCDMask3DSegLevelEncoder) is fed the backbone's per-level
+            # features (data_dict['voxel_pyramid']), or -- built with build_backbone=True -- runs the frozen backbone itself
             enc = build_module_by_name(cfg.model.get(inp + "_encoder"))
             if hasattr(enc, "_drop_base"):   # one dropout-site range per encoder instance
                 enc._drop_base = M.DROP_BASE_OBJ_ENC + (self.inputs.index(inp) << 12)
@@ -251,8 +251,20 @@ class Query3DUnified(nn.Module):
                 pos = fts_pos
             elif inp == "voxel":
                 # query3d_unified.py:146-152 with the backbone's outputs supplied: multi-scale LIST of segment features
-                feat = self.voxel_encoder(data_dict["voxel_pyramid"], data_dict["voxel2segment"],
-                                          max_seg=data_dict["seg_center"].shape[1])
+                max_seg = data_dict["seg_center"].shape[1]
+                pyramid, v2s = data_dict.get("voxel_pyramid"), data_dict["voxel2segment"]
+                if pyramid is None:   # query3d_unified.py:150-154: raw voxels through the frozen backbone (a supplied pyramid wins)
+                    vc = data_dict["voxel_coordinates"]
+                    # voxel2segment is the reference's per-scene list: the collated rows must be scene after scene, in list order
+                    # (building the pyramid synchronises anyway; nothing is checked when a pyramid is supplied)
+                    assert torch.bincount(vc[:, 0].long(), minlength=len(v2s)).tolist() == [int(p.numel()) for p in v2s] and \
+                        bool((vc[1:, 0] >= vc[:-1, 0]).all()), "voxel_coordinates must list scene 0's voxels, then scene 1's, ... as voxel2segment does"
+                    pyramid = self.voxel_encoder.voxel_pyramid(vc, data_dict["voxel_features"][:, :-3])
+                if torch.is_tensor(pyramid[0][0]):    # batched form (what the backbone produces): segment ids offset by b * max_seg
+                    ids = torch.cat([torch.where(p >= 0, p.long() + b * max_seg, p.long()) for b, p in enumerate(v2s)])
+                    feat = self.voxel_encoder(pyramid, ids, max_seg=max_seg, batch_size=data_dict["seg_center"].shape[0])
+                else:
+                    feat = self.voxel_encoder(pyramid, v2s, max_seg=max_seg)
                 mask = inv["seg_pad_masks"] if "seg_pad_masks" in inv else data_dict["seg_pad_masks"].logical_not()
                 pos = fts_pos
             else:

@@ -882,10 +882,14 @@ class ObjectEncoder(_PostNormBase):
 
 
 class PCDMask3DSegLevelEncoder(_PostNormBase):
-    """modules/vision/pcd_mask3d_encoder.py:114-154 WITHOUT its sparse-convolution backbone (Res16UNet34C on
-    MinkowskiEngine: SURVEY 2 'out of scope').  Everything after the backbone is here, with the reference's parameter
-    names (``feat_proj_list.{i}.{0,1}.{weight,bias}``: a checkpoint's post-backbone weights load; ``backbone.*`` keys are
-    not this module's): for every level in ``hlevels + [4]`` the level's voxel features are up-sampled to full resolution
+    """modules/vision/pcd_mask3d_encoder.py:114-154.  By default WITHOUT its sparse-convolution backbone: everything after
+    the backbone is here, with the reference's parameter names (``feat_proj_list.{i}.{0,1}.{weight,bias}``: a checkpoint's
+    post-backbone weights load; ``backbone.*`` keys are then not this module's).  With ``build_backbone=True`` (opt-in;
+    needs ``backbone_kwargs`` and ``freeze_backbone=True``) ``self.backbone`` is the frozen, forward-only ``Res16UNet34C`` on
+    the HIP sparse-convolution kernels (pq3d_amd/sparse.py) under the reference's ``backbone.*`` keys, and
+    ``voxel_pyramid(coords, feats)`` produces this module's ``pyramid`` input from raw voxels (Query3DUnified calls it when the
+    data_dict carries no ``voxel_pyramid``); training the backbone (``freeze_backbone=False``, the shipped stage-1 setting)
+    is not provided.  For every level in ``hlevels + [4]`` the level's voxel features are up-sampled to full resolution
     (``pooltr`` x (4 - hlevel), :127-131), mean-pooled per segment (``scatter_mean(..., dim_size=max_seg)``, :149) and
     projected (Linear + LayerNorm + Dropout, :122-126); the result is the multi-scale LIST the decoder indexes per layer
     (query_encoder.py:90-91) and whose last entry the mask head matches against (query3d_unified.py:163-165).
@@ -900,13 +904,30 @@ class PCDMask3DSegLevelEncoder(_PostNormBase):
     PLANES = (256, 256, 128, 96, 96)    # Res16UNet34C.PLANES[-5:] (res16unet.py:391)
 
     def __init__(self, cfg, backbone_kwargs=None, hidden_size=768, hlevels=(0, 1, 2, 3), freeze_backbone=False, dropout=0.1,
-                 sizes=None):
+                 sizes=None, build_backbone=False):
         super().__init__()
+        if build_backbone:
+            from .sparse import Res16UNet34C
+            if not freeze_backbone:
+                raise NotImplementedError("build_backbone=True provides the FROZEN voxel backbone only (freeze_backbone=True): "
+                                          "batch-statistics BatchNorm and the sparse-convolution backward are not provided")
+            assert backbone_kwargs is not None, "build_backbone=True needs backbone_kwargs (in_channels, out_channels, config)"
+            self.backbone = Res16UNet34C(**dict(backbone_kwargs))
+            assert sizes is None or tuple(sizes) == self.backbone.PLANES[-5:]
         self.sizes = tuple(sizes) if sizes is not None else self.PLANES
         self.hlevels = list(hlevels) + [4]      # 4 is for the last level, always used for mask seg features (:118)
         self.feat_proj_list = nn.ModuleList([nn.Sequential(nn.Linear(self.sizes[h], hidden_size), nn.LayerNorm(hidden_size),
                                                            nn.Dropout(dropout)) for h in self.hlevels])
         self.dropout_p, self._drop_base = float(dropout), DROP_BASE_OBJ_ENC + (7 << 12)
+
+    def voxel_pyramid(self, coords, feats):
+        """The backbone's per-level features and parent maps of raw voxels (``coords`` [N, 1+3] int32, ``feats`` [N, in_channels]),
+        in the batched form ``forward`` takes.  Needs ``build_backbone=True``."""
+        if not hasattr(self, "backbone"):
+            raise NotImplementedError("this PCDMask3DSegLevelEncoder was built without its backbone: pass build_backbone=True "
+                                      "(with backbone_kwargs, freeze_backbone=True) or supply data_dict['voxel_pyramid']")
+        self.backbone.compute = self.compute
+        return self.backbone.pyramid(coords, feats, self.hlevels[:-1])
 
     def forward(self, pyramid, point2segment, max_seg, batch_size=None):
         """Two input forms.  LIST form (the reference's decomposed features): ``pyramid[i] = ([feats_b], [parents_b])``,

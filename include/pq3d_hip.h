@@ -1169,7 +1169,7 @@ int pq3d_attn_causal_fwd(const void* qkv, const uint8_t* valid, void* out, int32
 int pq3d_l2norm_rows(const void* x, void* y, int64_t R, int32_t d, int32_t dt_x, int32_t dt_y, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Sparse 3-D convolution, forward (pq3d_amd/csrc/sparse_conv.hip; host side pq3d_amd/sparse.py).  Replaces the
+ * Sparse 3-D convolution, forward and input gradient (pq3d_amd/csrc/sparse_conv.hip; host side pq3d_amd/sparse.py).  Replaces the
  * MinkowskiConvolution / MinkowskiConvolutionTranspose + MinkowskiBatchNorm (eval) + residual add + MinkowskiReLU sequences
  * of the voxel backbone (modules/third_party/mask3d/res16unet.py:241-314, resnet_block.py:52-68), one launch per convolution:
  *     out[o, col_off + n] = act( (sum_k sum_c x[nbr[o, k], c] * W[k, c, n]) * scale[n] + shift[n] + bias[n] + residual[o, n] )
@@ -1209,10 +1209,79 @@ typedef struct {
   const float* residual;
   float* out;
   const uint32_t* occ;
+  int32_t wmode; /* how W is stored.  0: [K, Cin, Cout] (the forward).  1: [K, Cout, Cin] -- the call contracts over the LAST
+                    dimension of a forward weight, which makes it the input-gradient operator on the transposed kernel map:
+                    dX[i] = sum_k dY[nbrT[i, k]] W[k]^T (up[l] for a down[l] convolution and the reverse).  2: as 1 with the
+                    offset index reversed, W[K - 1 - k]: the centred (odd) kernels, whose map is its own transpose under offset
+                    reversal.  1 and 2 need Cin >= 16 or K = 1 (no packed path: the stem has no input gradient). */
 } pq3d_sparse_conv_desc;
 int pq3d_sparse_conv_fwd(const pq3d_sparse_conv_desc* d, void* stream);
 int pq3d_sparse_nbr(const int64_t* keys, int64_t n_in, const int32_t* q, int64_t n_out, const int32_t* offs, int32_t K,
                     int32_t* nbr, uint32_t* occ, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sparse 3-D convolution, backward, and batch-statistics BatchNorm over the rows of a level (pq3d_amd/csrc/sparse_conv_bwd.hip;
+ * host side pq3d_amd/sparse.py).  The input gradient is pq3d_sparse_conv_fwd with wmode 1 / 2 (above): its `residual`
+ * epilogue is the gradient accumulate of a tensor with two consumers.
+ *
+ * pq3d_sparse_conv_wgrad: dW[k, c, n] = sum_o x[nbr[o, k], c] * dy[o, n], fp32 [K, Cin, Cout], every element WRITTEN.
+ * x [N_in, ldx] fp32, dy [N_out, ldy] fp32 (rows of both may be column views of a wider buffer), nbr / occ as in the forward.
+ * A workgroup owns (offset k, 32 input channels, 64 output channels, one chunk of the row tiles): it walks the chunk's
+ * PQ3D_SPARSE_TILE-row tiles, skips a tile whose occupancy bit k is clear, gathers the x rows by index and reads the dy rows
+ * directly, both into [channel][row] LDS images (the contraction runs over rows), and keeps the accumulators in registers over
+ * the whole chunk.  The rows are split into S chunks of consecutive tiles: S = 1 stores dW directly; S > 1 stores partial slabs
+ * [S, K, Cin, Cout] into ws and a second kernel sums them in chunk order.  No atomics: for a given S the result is bitwise
+ * reproducible.  splits: 0 = S chosen from the sizes (pq3d_sparse_conv_wgrad_splits), else S itself (1 .. 4096; chunks beyond
+ * the last row tile hold zeros).  ws: at least pq3d_sparse_conv_wgrad_ws_bytes(N_out, Cin, Cout, K, splits) bytes, 16-byte
+ * aligned (0 bytes and ws may be NULL when S = 1); a smaller ws_bytes is refused before anything is launched.
+ * ct: PQ3D_F32 (exact-f32 MFMA) or PQ3D_BF16 (dy rounded to bf16, x carried as two bf16 planes hi + lo, fp32 accumulation:
+ * an offset with a single present pair is a one-term sum, which two rounded operands would put up to 2^-7 off).  Cin < 16
+ * (the stem) runs as one zero-padded 32-channel tile.
+ *
+ * BatchNorm over N rows, C channels (MinkowskiBatchNorm = BatchNorm1d over all rows of the batch), training mode:
+ *   pq3d_bn_stats      mean[c], rstd[c] = 1 / sqrt(biased variance + eps) of z [N, ldz]: per-block (count, mean, M2) partials
+ *                      of shifted sums (the shift is the block's first row, so nothing of the size of mean^2 is ever
+ *                      subtracted), combined in block order by Chan's formula: fixed summation order.  running_mean /
+ *                      running_var (optional, updated in place: (1 - momentum) old + momentum new, the variance unbiased,
+ *                      N / (N - 1); at N = 1 the factor is taken as 1) and num_batches_tracked (optional int64, += 1) are
+ *                      updated by the same call on the device.  part: workspace of pq3d_bn_ws_floats(N, C) floats.
+ *   pq3d_bn_apply      out[r, col_off + c] = act((z[r, c] - mean[c]) * rstd[c] * gamma[c] + beta[c] + residual[r, c])
+ *   pq3d_bn_bwd_reduce with g = dy * [y > 0] (y != NULL: the ReLU output) or g = dy: dbeta[c] = sum_r g, dgamma[c] = sum_r g
+ *                      xhat, xhat = (z - mean) rstd; per-block partials then a combine in block order (part: pq3d_bn_ws_floats).
+ *                      Both are WRITTEN.
+ *   pq3d_bn_bwd_apply  dz = gamma rstd (g - dbeta / N - xhat dgamma / N); dres (optional) <- g (dres_add = 0) or += g (1):
+ *                      the gradient of the residual branch.
+ * All row pointers take a leading dimension (outputs land at a column offset of the concatenation buffers).  Nothing
+ * synchronises with the host.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  int32_t N_out, N_in, Cin, Cout, K;
+  int32_t ct;
+  int32_t splits; /* 0 = chosen from the sizes; else the number of row chunks S */
+  int64_t ldx, ldy;
+  const float* x;
+  const int32_t* nbr;
+  const float* dy;
+  float* dW;
+  const uint32_t* occ;
+  float* ws;
+  int64_t ws_bytes;
+} pq3d_sparse_wgrad_desc;
+int pq3d_sparse_conv_wgrad(const pq3d_sparse_wgrad_desc* d, void* stream);
+int32_t pq3d_sparse_conv_wgrad_splits(int64_t N_out, int32_t Cin, int32_t Cout, int32_t K, int32_t splits);
+int64_t pq3d_sparse_conv_wgrad_ws_bytes(int64_t N_out, int32_t Cin, int32_t Cout, int32_t K, int32_t splits);
+
+int64_t pq3d_bn_ws_floats(int64_t N, int32_t C);
+int pq3d_bn_stats(const float* z, int64_t ldz, int64_t N, int32_t C, float eps, float momentum, float* mean, float* rstd,
+                  float* running_mean, float* running_var, int64_t* num_batches_tracked, float* part, void* stream);
+int pq3d_bn_apply(const float* z, int64_t ldz, int64_t N, int32_t C, const float* mean, const float* rstd, const float* gamma,
+                  const float* beta, const float* residual, int64_t ldr, int32_t act, float* out, int64_t ldo, int32_t col_off,
+                  void* stream);
+int pq3d_bn_bwd_reduce(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* z, int64_t ldz, int64_t N,
+                       int32_t C, const float* mean, const float* rstd, float* dgamma, float* dbeta, float* part, void* stream);
+int pq3d_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* z, int64_t ldz, int64_t N,
+                      int32_t C, const float* mean, const float* rstd, const float* gamma, const float* dgamma,
+                      const float* dbeta, float* dz, int64_t lddz, float* dres, int64_t lddres, int32_t dres_add, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange over RCCL / xGMI (SURVEY 8b's export list: pq3d_comm_init, pq3d_allreduce_grads; 8e).

@@ -212,7 +212,14 @@ class SparseConvDesc(C.Structure):
     """pq3d_sparse_conv_desc (csrc/sparse_conv.hip)."""
     _fields_ = [(n, C.c_int32) for n in ("N_out", "N_in", "Cin", "Cout", "K", "ct", "dtW", "act", "col_off", "ntl")] + \
                [(n, C.c_int64) for n in ("ldx", "ldo", "ldr")] + \
-               [(n, C.c_void_p) for n in ("x", "nbr", "W", "scale", "shift", "bias", "residual", "out", "occ")]
+               [(n, C.c_void_p) for n in ("x", "nbr", "W", "scale", "shift", "bias", "residual", "out", "occ")] + [("wmode", C.c_int32)]
+
+
+class SparseWgradDesc(C.Structure):
+    """pq3d_sparse_wgrad_desc (csrc/sparse_conv_bwd.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("N_out", "N_in", "Cin", "Cout", "K", "ct", "splits")] + \
+               [(n, C.c_int64) for n in ("ldx", "ldy")] + \
+               [(n, C.c_void_p) for n in ("x", "nbr", "dy", "dW", "occ", "ws")] + [("ws_bytes", C.c_int64)]
 
 
 _lib = None
@@ -368,6 +375,18 @@ _SIGS = {
     # sparse 3-D convolution + kernel maps of the voxel backbone (csrc/sparse_conv.hip)
     "pq3d_sparse_conv_fwd": [C.POINTER(SparseConvDesc), C.c_void_p],
     "pq3d_sparse_nbr": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    # sparse-convolution weight gradient and batch-statistics BatchNorm (csrc/sparse_conv_bwd.hip)
+    "pq3d_sparse_conv_wgrad": [C.POINTER(SparseWgradDesc), C.c_void_p],
+    "pq3d_sparse_conv_wgrad_splits": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32],
+    "pq3d_sparse_conv_wgrad_ws_bytes": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32],
+    "pq3d_bn_ws_floats": [C.c_int64, C.c_int32],
+    "pq3d_bn_stats": [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float] + [C.c_void_p] * 7,
+    "pq3d_bn_apply": [C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                                                      C.c_int32, C.c_void_p],
+    "pq3d_bn_bwd_reduce": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32] +
+                          [C.c_void_p] * 6,
+    "pq3d_bn_bwd_apply": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32] +
+                         [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     # data-parallel gradient exchange over RCCL (csrc/comm.hip)
     "pq3d_comm_unique_id": [C.c_void_p],
     "pq3d_comm_init": [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],
@@ -378,7 +397,8 @@ _SIGS = {
     "pq3d_allreduce_grads_wire": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "pq3d_test_wire_reduce": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
 }
-_RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes"}   # size queries: bytes (or -1), not a status code
+_RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
+          "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats"}   # size queries: bytes (or -1), not a status code
 EXPORTS = sorted(list(_SIGS) + ["pq3d_last_error", "pq3d_version"])
 
 

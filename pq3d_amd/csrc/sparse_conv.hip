@@ -1,5 +1,6 @@
-// Sparse 3-D convolution forward + kernel maps for the voxel backbone (pq3d_amd/sparse.py; reference: Res16UNet34C on
-// MinkowskiEngine, modules/third_party/mask3d/res16unet.py -- frozen, forward only).  Definition in include/pq3d_hip.h.
+// Sparse 3-D convolution forward (and, by descriptor field wmode, input gradient) + kernel maps for the voxel backbone
+// (pq3d_amd/sparse.py; reference: Res16UNet34C on MinkowskiEngine, modules/third_party/mask3d/res16unet.py).  The weight
+// gradient and batch-statistics BatchNorm are in sparse_conv_bwd.hip.  Definition in include/pq3d_hip.h.
 //   pq3d_sparse_conv_fwd  out[o] = act((sum_k x[nbr[o, k]] W[k]) * scale + shift + bias + residual[o]), output-stationary:
 //                         a workgroup (4 waves) owns 64 output rows x 16 NTL output channels; wave w owns rows 16 w .. 16 w + 15.
 //                         Per present offset k and per 32-channel chunk of Cin: the 64 neighbour rows are gathered by index
@@ -98,16 +99,30 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_conv_kernel(const pq3d_spar
         *(float4*)((float*)As + ar * LDR + ac + 4) = make_float4(v[4], v[5], v[6], v[7]);
       }
       // ---- B: W[k][c0 .. c0 + 32)[n0 .. n0 + TN) -> Bs[n][c]
-      for (int u = tid; u < SC_KC * (TN / 8); u += SC_THREADS) {
-        const int kk = u / (TN / 8), nn = (u - kk * (TN / 8)) * 8;
-        const int c = c0 + kk;
-        float w[8];
+      if (!PACKED && d.wmode) {   // W stored [K, Cout, Cin] (the input gradient): the chunk is contiguous along c, no transpose
+        const int kw = d.wmode == 2 ? K - 1 - k : k;
+        for (int u = tid; u < TN * (SC_KC / 8); u += SC_THREADS) {
+          const int nn = u / (SC_KC / 8), kk = (u - nn * (SC_KC / 8)) * 8;
+          float w[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = 0.f;
-        if (c < clen && n0 + nn < Cout)
-          load_elems<8>(d.W, d.dtW, ((long)k * Cin + c) * Cout + n0 + nn, Cout - (n0 + nn), w);
+          for (int j = 0; j < 8; ++j) w[j] = 0.f;
+          if (n0 + nn < Cout && c0 + kk < Cin)
+            load_elems<8>(d.W, d.dtW, ((long)kw * Cout + n0 + nn) * Cin + c0 + kk, Cin - (c0 + kk), w);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) Bs[(nn + j) * LDR + kk] = Cvt<CT>::from(w[j]);
+          for (int j = 0; j < 8; ++j) Bs[nn * LDR + kk + j] = Cvt<CT>::from(w[j]);
+        }
+      } else {
+        for (int u = tid; u < SC_KC * (TN / 8); u += SC_THREADS) {
+          const int kk = u / (TN / 8), nn = (u - kk * (TN / 8)) * 8;
+          const int c = c0 + kk;
+          float w[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) w[j] = 0.f;
+          if (c < clen && n0 + nn < Cout)
+            load_elems<8>(d.W, d.dtW, ((long)k * Cin + c) * Cout + n0 + nn, Cout - (n0 + nn), w);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) Bs[(nn + j) * LDR + kk] = Cvt<CT>::from(w[j]);
+        }
       }
       __syncthreads();
 #pragma unroll
@@ -233,6 +248,7 @@ extern "C" int pq3d_sparse_conv_fwd(const pq3d_sparse_conv_desc* dp, void* strea
                "pq3d_sparse_conv_fwd: misaligned pointer");
   const long tiles = ((long)d.N_out + SC_T - 1) / SC_T;
   const bool packed = d.Cin < 16 && d.K > 1;
+  PQ_CHECK_ARG(d.wmode >= 0 && d.wmode <= 2 && !(packed && d.wmode), "pq3d_sparse_conv_fwd: wmode must be 0, 1 or 2 (1, 2: Cin >= 16 or K = 1)");
   PQ_CHECK_ARG(d.ntl == 0 || d.ntl == 2 || d.ntl == 4 || d.ntl == 6 || d.ntl == 8, "pq3d_sparse_conv_fwd: ntl must be 0, 2, 4, 6 or 8");
   const int ntl = d.ntl ? d.ntl : pick_ntl(tiles, d.Cout);
   PQ_CHECK_ARG((d.Cout + 16 * ntl - 1) / (16 * ntl) <= 65535, "pq3d_sparse_conv_fwd: Cout too large");

@@ -95,7 +95,7 @@ class Query3DUnified(nn.Module):
                 continue
             # voxel without use_offline_voxel_fts: the reference runs its MinkowskiEngine backbone inside the model
             # (query3d_unified.py:146-152); here the voxel encoder (M.PCDMask3DSegLevelEncoder) is fed the backbone's per-level
-            # features (data_dict['voxel_pyramid']), or -- built with build_backbone=True -- runs the frozen backbone itself
+            # features (data_dict['voxel_pyramid']), or -- built with build_backbone=True / 'trainable' -- runs the backbone itself
             enc = build_module_by_name(cfg.model.get(inp + "_encoder"))
             if hasattr(enc, "_drop_base"):   # one dropout-site range per encoder instance
                 enc._drop_base = M.DROP_BASE_OBJ_ENC + (self.inputs.index(inp) << 12)
@@ -253,7 +253,7 @@ class Query3DUnified(nn.Module):
                 # query3d_unified.py:146-152 with the backbone's outputs supplied: multi-scale LIST of segment features
                 max_seg = data_dict["seg_center"].shape[1]
                 pyramid, v2s = data_dict.get("voxel_pyramid"), data_dict["voxel2segment"]
-                if pyramid is None:   # query3d_unified.py:150-154: raw voxels through the frozen backbone (a supplied pyramid wins)
+                if pyramid is None:   # query3d_unified.py:150-154: raw voxels through the backbone (a supplied pyramid wins)
                     vc = data_dict["voxel_coordinates"]
                     # voxel2segment is the reference's per-scene list: the collated rows must be scene after scene, in list order
                     # (building the pyramid synchronises anyway; nothing is checked when a pyramid is supplied)
@@ -333,11 +333,15 @@ class Query3DUnified(nn.Module):
         ``encoder_outputs`` (modules/heads/generation_head.py: the decoder cross-attends to the query tokens).  The shared
         token embedding is used by the decoder and stays.  TrainStep keeps these out of the flat optimizer (torch.optim.AdamW
         in the reference skips grad-None parameters)."""
+        out = []
+        backbone = getattr(getattr(self, "voxel_encoder", None), "backbone", None)
+        if backbone is not None and hasattr(backbone, "unused_parameters"):
+            out += backbone.unused_parameters()      # a trainable voxel backbone's `final.*`: its forward never applies it
         head = getattr(self, "generation_head", None)
         if head is None:
-            return []
+            return out
         shared = {id(p) for p in head.model.shared.parameters()}
-        return [p for p in head.model.encoder.parameters() if id(p) not in shared]
+        return out + [p for p in head.model.encoder.parameters() if id(p) not in shared]
 
     def get_opt_params(self):
         """model/query3d_unified.py:224-238."""

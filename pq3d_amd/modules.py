@@ -888,8 +888,9 @@ class PCDMask3DSegLevelEncoder(_PostNormBase):
     needs ``backbone_kwargs`` and ``freeze_backbone=True``) ``self.backbone`` is the frozen, forward-only ``Res16UNet34C`` on
     the HIP sparse-convolution kernels (pq3d_amd/sparse.py) under the reference's ``backbone.*`` keys, and
     ``voxel_pyramid(coords, feats)`` produces this module's ``pyramid`` input from raw voxels (Query3DUnified calls it when the
-    data_dict carries no ``voxel_pyramid``); training the backbone (``freeze_backbone=False``, the shipped stage-1 setting)
-    is not provided.  For every level in ``hlevels + [4]`` the level's voxel features are up-sampled to full resolution
+    data_dict carries no ``voxel_pyramid``).  ``build_backbone="trainable"`` with ``freeze_backbone=False`` (the shipped
+    stage-1 setting) builds ``Res16UNet34C(trainable=True)``: batch-statistics BatchNorm (per rank, as torch DDP without
+    SyncBatchNorm) and the sparse-convolution backward, its parameters in this module's optimizer group.  For every level in ``hlevels + [4]`` the level's voxel features are up-sampled to full resolution
     (``pooltr`` x (4 - hlevel), :127-131), mean-pooled per segment (``scatter_mean(..., dim_size=max_seg)``, :149) and
     projected (Linear + LayerNorm + Dropout, :122-126); the result is the multi-scale LIST the decoder indexes per layer
     (query_encoder.py:90-91) and whose last entry the mask head matches against (query3d_unified.py:163-165).
@@ -908,11 +909,14 @@ class PCDMask3DSegLevelEncoder(_PostNormBase):
         super().__init__()
         if build_backbone:
             from .sparse import Res16UNet34C
-            if not freeze_backbone:
+            assert build_backbone is True or build_backbone == "trainable", "build_backbone is False, True or 'trainable'"
+            if not freeze_backbone and build_backbone is True:
                 raise NotImplementedError("build_backbone=True provides the FROZEN voxel backbone only (freeze_backbone=True): "
                                           "batch-statistics BatchNorm and the sparse-convolution backward are not provided")
             assert backbone_kwargs is not None, "build_backbone=True needs backbone_kwargs (in_channels, out_channels, config)"
-            self.backbone = Res16UNet34C(**dict(backbone_kwargs))
+            # 'trainable' with freeze_backbone=False: batch-statistics BatchNorm and the sparse-convolution backward
+            # (Res16UNet34C(trainable=True)); with freeze_backbone=True it is the frozen network, as build_backbone=True
+            self.backbone = Res16UNet34C(**dict(backbone_kwargs), trainable=not freeze_backbone)
             assert sizes is None or tuple(sizes) == self.backbone.PLANES[-5:]
         self.sizes = tuple(sizes) if sizes is not None else self.PLANES
         self.hlevels = list(hlevels) + [4]      # 4 is for the last level, always used for mask seg features (:118)

@@ -1,4 +1,5 @@
-"""Sparse-convolution voxel backbone on the HIP kernels: coordinate pyramid, kernel maps and Res16UNet34C (frozen, forward only).
+"""Sparse-convolution voxel backbone on the HIP kernels: coordinate pyramid, kernel maps, the convolution's forward and backward
+operators, batch-statistics BatchNorm, and Res16UNet34C (frozen and forward only by default; ``trainable=True`` trains it).
 
 Reference: ``PCDMask3DSegLevelEncoder.backbone`` = ``Res16UNet34C`` on MinkowskiEngine (modules/vision/pcd_mask3d_encoder.py:121,
 modules/third_party/mask3d/res16unet.py:28-314,390-391, resnet.py:99-152, resnet_block.py:7-68).  MinkowskiEngine cannot be run
@@ -20,7 +21,7 @@ convolution kernel are then neighbours in space and share most of their gathered
 ``Res16UNet34C.forward`` returns at full resolution are in the caller's row order.
 
 Building a ``CoordPyramid`` needs the level sizes on the host (``torch.unique``): one synchronisation per batch, outside any
-graph.  Everything ``Res16UNet34C.run`` launches afterwards is capturable.
+graph.  Everything ``Res16UNet34C.run`` launches afterwards -- the training forward and its backward included -- is capturable.
 """
 from __future__ import annotations
 
@@ -136,14 +137,8 @@ class CoordPyramid:
 
 
 # ------------------------------------------------------------------------------------------------ the operator
-def sparse_conv(x: torch.Tensor, kmap: KernelMap, W: torch.Tensor, *, ct: int = F32, scale=None, shift=None, bias=None,
-                residual=None, act: Optional[str] = None, out: Optional[torch.Tensor] = None, col_off: int = 0,
-                use_occ: bool = True, ntl: int = 0) -> torch.Tensor:
-    """out[:, col_off : col_off + Cout] = act((sum_k x[nbr[:, k]] @ W[k]) * scale + shift + bias + residual), one launch
-    (pq3d_sparse_conv_fwd).  ``x`` [N_in, Cin] and ``residual`` [N_out, Cout] fp32, rows may be strided (column views of a
-    wider buffer); ``W`` [K, Cin, Cout] fp32 or bf16; ``out`` [N_out, >= col_off + Cout] fp32 (allocated when None).
-    ``ntl``: output channels per workgroup / 16 (2, 4, 6 or 8; 0 = the library's choice) -- no output bit depends on it."""
-    K, Cin, Cout = W.shape
+def _conv_launch(x, kmap, W, Cin, Cout, wmode, ct, scale, shift, bias, residual, act, out, col_off, use_occ, ntl):
+    K = W.shape[0]
     assert x.dtype == torch.float32 and x.dim() == 2 and x.shape == (kmap.n_in, Cin) and x.stride(1) == 1, "x is [N_in, Cin] fp32"
     assert kmap.K == K and W.is_contiguous() and kmap.nbr.is_contiguous()
     if out is None:
@@ -152,7 +147,7 @@ def sparse_conv(x: torch.Tensor, kmap: KernelMap, W: torch.Tensor, *, ct: int = 
     assert out.shape[1] >= col_off + Cout
     d = L.SparseConvDesc()
     d.N_out, d.N_in, d.Cin, d.Cout, d.K = kmap.n_out, kmap.n_in, Cin, Cout, K
-    d.ct, d.dtW, d.act, d.col_off, d.ntl = ct, L.dt_of(W), _ACT[act], col_off, ntl
+    d.ct, d.dtW, d.act, d.col_off, d.ntl, d.wmode = ct, L.dt_of(W), _ACT[act], col_off, ntl, wmode
     d.ldx, d.ldo = x.stride(0), out.stride(0)
     d.x, d.nbr, d.W, d.out = L.ptr(x), L.ptr(kmap.nbr), L.ptr(W), L.ptr(out)
     for name, t in (("scale", scale), ("shift", shift), ("bias", bias)):
@@ -165,8 +160,144 @@ def sparse_conv(x: torch.Tensor, kmap: KernelMap, W: torch.Tensor, *, ct: int = 
     if use_occ:
         d.occ = L.ptr(kmap.occ)
     esz = 2 if W.dtype == torch.bfloat16 else 4
-    L.call("pq3d_sparse_conv_fwd", d, work=(f"No{kmap.n_out}Ni{kmap.n_in}Ci{Cin}Co{Cout}K{K}ct{ct}", 2.0 * kmap.n_out * K * Cin * Cout,
+    L.call("pq3d_sparse_conv_fwd", d, work=(f"No{kmap.n_out}Ni{kmap.n_in}Ci{Cin}Co{Cout}K{K}ct{ct}" + (f"w{wmode}" if wmode else ""),
+                                            2.0 * kmap.n_out * K * Cin * Cout,
                                             4.0 * kmap.n_in * Cin + 4.0 * kmap.n_out * (K + Cout) + esz * K * Cin * Cout))
+    return out
+
+
+def sparse_conv(x: torch.Tensor, kmap: KernelMap, W: torch.Tensor, *, ct: int = F32, scale=None, shift=None, bias=None,
+                residual=None, act: Optional[str] = None, out: Optional[torch.Tensor] = None, col_off: int = 0,
+                use_occ: bool = True, ntl: int = 0) -> torch.Tensor:
+    """out[:, col_off : col_off + Cout] = act((sum_k x[nbr[:, k]] @ W[k]) * scale + shift + bias + residual), one launch
+    (pq3d_sparse_conv_fwd).  ``x`` [N_in, Cin] and ``residual`` [N_out, Cout] fp32, rows may be strided (column views of a
+    wider buffer); ``W`` [K, Cin, Cout] fp32 or bf16; ``out`` [N_out, >= col_off + Cout] fp32 (allocated when None).
+    ``ntl``: output channels per workgroup / 16 (2, 4, 6 or 8; 0 = the library's choice) -- no output bit depends on it."""
+    K, Cin, Cout = W.shape
+    return _conv_launch(x, kmap, W, Cin, Cout, 0, ct, scale, shift, bias, residual, act, out, col_off, use_occ, ntl)
+
+
+def sparse_conv_bwd_input(dy: torch.Tensor, kmap_t: KernelMap, W: torch.Tensor, reverse_k: bool = False, *, ct: int = F32,
+                          residual=None, out: Optional[torch.Tensor] = None, col_off: int = 0, use_occ: bool = True,
+                          ntl: int = 0) -> torch.Tensor:
+    """Input gradient of ``sparse_conv``: out[:, col_off : col_off + Cin] = sum_k dy[kmap_t.nbr[:, k]] @ W[k'].T + residual with
+    ``W`` the FORWARD weight [K, Cin, Cout] as it is stored (the kernel reads it transposed: no copy).  ``kmap_t`` is the
+    transpose of the forward's map: ``up[l]`` for a ``down[l]`` convolution and the reverse with k' = k; for the centred
+    kernels the same ``nbr3`` / ``nbr5`` map with ``reverse_k=True`` (k' = K - 1 - k).  ``dy`` [kmap_t.n_in, Cout] fp32, rows may
+    be strided; ``residual`` [kmap_t.n_out, Cin] is added in the epilogue -- the gradient accumulate of a tensor with a second
+    consumer.  An input row no output row uses gets exact zeros (+ residual)."""
+    K, Cin, Cout = W.shape
+    return _conv_launch(dy, kmap_t, W, Cout, Cin, 2 if reverse_k else 1, ct, None, None, None, residual, None, out, col_off,
+                        use_occ, ntl)
+
+
+def wgrad_splits(n_out: int, Cin: int, Cout: int, K: int, splits: int = 0) -> int:
+    """The number of row chunks ``sparse_conv_bwd_weight`` uses (``splits`` = 0: the library's choice from the sizes)."""
+    S = int(L.lib().pq3d_sparse_conv_wgrad_splits(n_out, Cin, Cout, K, splits))
+    if S < 1:
+        raise L.Pq3dError("pq3d_sparse_conv_wgrad_splits: splits must be 0 (chosen from the sizes) or 1 .. 4096")
+    return S
+
+
+def sparse_conv_bwd_weight(x: torch.Tensor, kmap: KernelMap, dy: torch.Tensor, *, ct: int = F32, splits: int = 0,
+                           out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, use_occ: bool = True) -> torch.Tensor:
+    """Weight gradient of ``sparse_conv``: dW[k] = x[kmap.nbr[:, k]].T @ dy, [K, Cin, Cout] fp32, every element written
+    (pq3d_sparse_conv_wgrad).  ``x`` [N_in, Cin], ``dy`` [N_out, Cout] fp32, rows may be strided.  The rows are cut into
+    ``splits`` chunks (0 = chosen from the sizes) whose partial slabs are summed in chunk order: no atomics, the same bits run
+    to run for a given ``splits``.  ``ws``: fp32 workspace (allocated when None; a given one that is too small is refused)."""
+    Cin, Cout, K = x.shape[1], dy.shape[1], kmap.K
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] == kmap.n_in and x.stride(1) == 1, "x is [N_in, Cin] fp32"
+    assert dy.dtype == torch.float32 and dy.dim() == 2 and dy.shape[0] == kmap.n_out and dy.stride(1) == 1, "dy is [N_out, Cout] fp32"
+    assert kmap.nbr.is_contiguous()
+    if out is None:
+        out = torch.empty(K, Cin, Cout, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (K, Cin, Cout) and out.is_contiguous()
+    need = int(L.lib().pq3d_sparse_conv_wgrad_ws_bytes(kmap.n_out, Cin, Cout, K, splits))
+    if need < 0:
+        raise L.Pq3dError("pq3d_sparse_conv_wgrad_ws_bytes: splits must be 0 (chosen from the sizes) or 1 .. 4096")
+    if ws is None and need:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    d = L.SparseWgradDesc()
+    d.N_out, d.N_in, d.Cin, d.Cout, d.K, d.ct, d.splits = kmap.n_out, kmap.n_in, Cin, Cout, K, ct, splits
+    d.ldx, d.ldy = x.stride(0), dy.stride(0)
+    d.x, d.nbr, d.dy, d.dW = L.ptr(x), L.ptr(kmap.nbr), L.ptr(dy), L.ptr(out)
+    if ws is not None:
+        assert ws.dtype == torch.float32 and ws.is_contiguous()
+        d.ws, d.ws_bytes = L.ptr(ws), ws.numel() * 4
+    if use_occ:
+        d.occ = L.ptr(kmap.occ)
+    L.call("pq3d_sparse_conv_wgrad", d, work=(f"No{kmap.n_out}Ni{kmap.n_in}Ci{Cin}Co{Cout}K{K}ct{ct}", 2.0 * kmap.n_out * K * Cin * Cout,
+                                              4.0 * kmap.n_in * Cin + 4.0 * kmap.n_out * (K + Cout) + 4.0 * K * Cin * Cout + 2.0 * need))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ batch-statistics BatchNorm
+def _rows(t, C, name):
+    assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == C and t.stride(1) == 1, f"{name} is [N, C] fp32 (rows may be strided)"
+    return t
+
+
+def _bn_part(N: int, C: int, dev) -> torch.Tensor:
+    return torch.empty(int(L.lib().pq3d_bn_ws_floats(N, C)), dtype=torch.float32, device=dev)
+
+
+def bn_stats(z: torch.Tensor, eps: float, momentum: float = 0.0, running_mean=None, running_var=None, num_batches_tracked=None):
+    """(mean, rstd) [C] of the rows of ``z`` [N, C] (biased variance, rstd = 1 / sqrt(var + eps)), summed in a fixed order without
+    ever forming E[x^2] - mean^2.  The running buffers (optional) are updated in place on the device as nn.BatchNorm1d does in
+    training mode: (1 - momentum) old + momentum new with the unbiased variance, ``num_batches_tracked`` += 1."""
+    N, C = z.shape
+    _rows(z, C, "z")
+    mean, rstd = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
+    for t in (running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (C,) and t.is_contiguous())
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.numel() == 1)
+    L.call("pq3d_bn_stats", z, z.stride(0), N, C, float(eps), float(momentum), mean, rstd, running_mean, running_var,
+           num_batches_tracked, _bn_part(N, C, z.device), work=(f"N{N}C{C}", 4.0 * N * C, 4.0 * N * C))
+    return mean, rstd
+
+
+def bn_apply(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, residual=None,
+             act: Optional[str] = None, out: Optional[torch.Tensor] = None, col_off: int = 0) -> torch.Tensor:
+    """out[:, col_off : col_off + C] = act((z - mean) * rstd * weight + bias + residual); returns that column view."""
+    N, C = z.shape
+    _rows(z, C, "z")
+    if out is None:
+        out = torch.empty(N, col_off + C, dtype=torch.float32, device=z.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == N and out.stride(1) == 1 and out.shape[1] >= col_off + C
+    if residual is not None:
+        _rows(residual, C, "residual")
+        assert residual.shape[0] == N
+    L.call("pq3d_bn_apply", z, z.stride(0), N, C, mean, rstd, weight, bias, residual, residual.stride(0) if residual is not None else 0,
+           _ACT[act], out, out.stride(0), col_off, work=(f"N{N}C{C}", 4.0 * N * C, (12.0 if residual is not None else 8.0) * N * C))
+    return out[:, col_off:col_off + C]
+
+
+def bn_bwd_reduce(dy: torch.Tensor, z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, y: Optional[torch.Tensor] = None):
+    """(dweight, dbias) [C]: sum_r g xhat and sum_r g with g = dy * [y > 0] (``y``: the ReLU output) or g = dy; fixed order."""
+    N, C = z.shape
+    _rows(z, C, "z"); _rows(dy, C, "dy")
+    assert dy.shape[0] == N and (y is None or (_rows(y, C, "y").shape[0] == N))
+    dg, db = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
+    L.call("pq3d_bn_bwd_reduce", dy, dy.stride(0), y, y.stride(0) if y is not None else 0, z, z.stride(0), N, C, mean, rstd, dg, db,
+           _bn_part(N, C, z.device), work=(f"N{N}C{C}", 5.0 * N * C, (12.0 if y is not None else 8.0) * N * C))
+    return dg, db
+
+
+def bn_bwd_apply(dy: torch.Tensor, z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, weight: torch.Tensor, dweight: torch.Tensor,
+                 dbias: torch.Tensor, *, y: Optional[torch.Tensor] = None, dres: Optional[torch.Tensor] = None, dres_add: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dz = weight rstd (g - dbias / N - xhat dweight / N) with (dweight, dbias) of ``bn_bwd_reduce``; ``dres`` [N, C] (optional,
+    rows may be strided) receives g, the gradient of the residual branch: written, or added with ``dres_add``."""
+    N, C = z.shape
+    _rows(z, C, "z"); _rows(dy, C, "dy")
+    assert dy.shape[0] == N and (y is None or (_rows(y, C, "y").shape[0] == N))
+    if out is None:
+        out = torch.empty(N, C, dtype=torch.float32, device=z.device)
+    _rows(out, C, "out")
+    assert out.shape[0] == N and (dres is None or _rows(dres, C, "dres").shape[0] == N)
+    L.call("pq3d_bn_bwd_apply", dy, dy.stride(0), y, y.stride(0) if y is not None else 0, z, z.stride(0), N, C, mean, rstd, weight,
+           dweight, dbias, out, out.stride(0), dres, dres.stride(0) if dres is not None else 0, int(dres_add),
+           work=(f"N{N}C{C}", 8.0 * N * C, 16.0 * N * C))
     return out
 
 
@@ -179,6 +310,25 @@ def row_gemm(x: torch.Tensor, Wt: torch.Tensor, bias: Optional[torch.Tensor], ct
     if x.shape[0]:
         L.gemm(M=x.shape[0], N=Cout, K=Cin, A=[x], B=[Wt], bias=[bias], Cs=[y], ct=ct, lda=x.stride(0), ldb=Cin, ldc=Cout, act=act)
     return y
+
+
+def _gemm_raw(x: torch.Tensor, W: torch.Tensor, ct: int) -> torch.Tensor:
+    """x @ W with the K = 1 convolution's kernel as it is stored ([Cin, Cout] fp32): the training forward of a ``downsample``."""
+    Cin, Cout = W.shape
+    y = torch.empty(x.shape[0], Cout, dtype=torch.float32, device=x.device)
+    L.gemm(M=x.shape[0], N=Cout, K=Cin, A=[x], B=[W], Cs=[y], ct=ct, lda=x.stride(0), ldb=Cout, ldc=Cout, transB=True)
+    return y
+
+
+def _gemm_raw_bwd(x: torch.Tensor, W: torch.Tensor, dz: torch.Tensor, ct: int):
+    """(dx, dW) of ``_gemm_raw``: dz @ W.T and x.T @ dz (one writer per element: no split-K atomics)."""
+    Cin, Cout = W.shape
+    R = x.shape[0]
+    dx = torch.empty(R, Cin, dtype=torch.float32, device=x.device)
+    dW = torch.empty(Cin, Cout, dtype=torch.float32, device=x.device)
+    L.gemm(M=R, N=Cin, K=Cout, A=[dz], B=[W], Cs=[dx], ct=ct, lda=dz.stride(0), ldb=Cout, ldc=Cin)
+    L.gemm(M=Cin, N=Cout, K=R, A=[x], B=[dz], Cs=[dW], ct=ct, lda=x.stride(0), ldb=dz.stride(0), ldc=Cout, transA=True, transB=True)
+    return dx, dW
 
 
 # ------------------------------------------------------------------------------------------------ modules
@@ -196,7 +346,8 @@ class SparseConv(nn.Module):
 
 
 class SparseBatchNorm(nn.Module):
-    """MinkowskiBatchNorm's layout: the statistics live in ``.bn`` (an nn.BatchNorm1d).  Eval mode only."""
+    """MinkowskiBatchNorm's layout: the statistics live in ``.bn`` (an nn.BatchNorm1d).  Parameters and buffers only: the
+    arithmetic (folded in eval mode, batch statistics in training mode) is Res16UNet34C.run's."""
 
     def __init__(self, c: int, momentum: float = 0.1):
         super().__init__()
@@ -215,6 +366,42 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
 
+class _BackboneTrain(torch.autograd.Function):
+    """Res16UNet34C's training forward and backward as ONE autograd node: inputs are every kernel / bn.weight / bn.bias in
+    ``layers`` order, outputs the five feature maps."""
+
+    @staticmethod
+    def forward(ctx, net, pyr, layers, feats, *params):
+        tape = {}
+        outs = net._train_forward(pyr, feats, layers, tape)
+        # the coarse maps are outputs AND tape entries (the ReLU mask of their own layer, the input of the next transposed
+        # convolution): those go through save_for_backward.  An output kept as a plain attribute ties the node to its own
+        # result -- the graph, with the parameters' AccumulateGrad nodes of the stream it ran on, would outlive the step.
+        pos = {id(o): i for i, o in enumerate(outs[:4])}
+        for t in tape.values():
+            for key in ("x", "y"):
+                if id(t[key]) in pos:
+                    t[key] = pos[id(t[key])]
+        assert sum(isinstance(t[key], int) for t in tape.values() for key in ("x", "y")) == 8
+        ctx.save_for_backward(*outs[:4])
+        ctx.net, ctx.pyr, ctx.layers, ctx.tape = net, pyr, layers, tape
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, g16, g8, g4, g2, gout):
+        tape = {k: dict(v) for k, v in ctx.tape.items()}
+        saved = ctx.saved_tensors
+        for t in tape.values():
+            for key in ("x", "y"):
+                if isinstance(t[key], int):
+                    t[key] = saved[t[key]]
+        cg = lambda g: None if g is None else g.float().contiguous()
+        grads = ctx.net._train_backward(ctx.pyr, ctx.layers, tape, cg(g16), cg(g8), cg(g4), cg(g2), gout)
+        flat = [g for name, _c, _n in ctx.layers for g in grads[name]]
+        return (None, None, None, None, *flat)
+
+
 class Res16UNet34C(nn.Module):
     """res16unet.py:28-314 with BLOCK = BasicBlock, LAYERS = (2, 3, 4, 6, 2, 2, 2, 2), PLANES = (32, 64, 128, 256, 256, 128, 96,
     96): the reference's parameter and buffer names, so a checkpoint's ``voxel_encoder.backbone.*`` entries load.  FROZEN and
@@ -230,16 +417,26 @@ class Res16UNet34C(nn.Module):
     (-2^19, 2^19) voxels (the packing of the sort keys; ``CoordPyramid`` refuses anything else).
 
     ``prepare()`` runs at the first forward and again after ``load_state_dict`` / ``.to()`` / a change of ``compute``; after
-    editing a parameter or buffer IN PLACE call ``prepare(force=True)``."""
+    editing a parameter or buffer IN PLACE call ``prepare(force=True)``.
+
+    ``trainable=True``: parameters require grad and ``train()`` / ``eval()`` behave as on any module.  In training mode ``run``
+    executes convolution (raw fp32 weights, converted in the kernel) -> batch statistics -> normalise for every layer, updates the
+    running buffers on the device, and returns the five maps from ONE autograd node whose backward walks the recorded tape in
+    reverse (input gradient = the forward kernel on the transposed map, weight gradient over row chunks without atomics,
+    BatchNorm backward; ``'bf16'`` and ``'bf16x3'`` both mean bf16 operands there).  Batch statistics are per process (no
+    SyncBatchNorm).  ``final.*`` never gets a gradient: ``unused_parameters()`` lists it.  In eval mode a trainable module runs
+    the folded path above under ``no_grad``, folding afresh at every forward (its weights change under the optimizer);
+    with grad enabled it raises."""
 
     PLANES = (32, 64, 128, 256, 256, 128, 96, 96)
     LAYERS = (2, 3, 4, 6, 2, 2, 2, 2)
     INIT_DIM = 32
 
-    def __init__(self, in_channels: int, out_channels: int, config, out_fpn: bool = True, D: int = 3, compute: str = "fp32"):
+    def __init__(self, in_channels: int, out_channels: int, config, out_fpn: bool = True, D: int = 3, compute: str = "fp32",
+                 trainable: bool = False):
         super().__init__()
         assert D == 3, "the 3-D network only"
-        self.out_fpn, self.compute = out_fpn, compute
+        self.out_fpn, self.compute, self.trainable = out_fpn, compute, bool(trainable)
         mom = float(config["bn_momentum"])
         P = self.PLANES
         self.inplanes = self.INIT_DIM
@@ -259,6 +456,8 @@ class Res16UNet34C(nn.Module):
         self.final = SparseConv(P[7], out_channels, 1, bias=True)
         del self.inplanes
         self._prep = None
+        if self.trainable:
+            return                      # parameters require grad, training mode: as any freshly built module
         self.requires_grad_(False)
         self.eval()
 
@@ -273,6 +472,8 @@ class Res16UNet34C(nn.Module):
 
     # ---- frozen-only contract
     def train(self, mode: bool = True):
+        if self.trainable:
+            return super().train(mode)
         if mode and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("Res16UNet34C on the HIP kernels is the FROZEN backbone (BatchNorm in eval mode, "
                                       "PCDMask3DSegLevelEncoder(freeze_backbone=True)); batch-statistics BatchNorm and the "
@@ -294,7 +495,9 @@ class Res16UNet34C(nn.Module):
     def prepare(self, force: bool = False):
         """Fold every BatchNorm (eval) into scale / shift and convert every kernel (K = 1 included) to the compute type, once."""
         key = (self.ct, self.conv0p1s1.kernel.device)
-        if not force and self._prep is not None and self._prep["key"] == key:
+        # a trainable network's weights move under an optimizer that updates them in place (TrainStep's flat AdamW leaves no
+        # trace on the module): its eval-mode forward folds afresh every time instead of trusting a cache
+        if not force and not self.trainable and self._prep is not None and self._prep["key"] == key:
             return self._prep
         wdt = torch.bfloat16 if self.ct == BF16 else torch.float32
         P = {"key": key}
@@ -327,6 +530,8 @@ class Res16UNet34C(nn.Module):
     # ---- the launches (capturable)
     def run(self, pyr: CoordPyramid, feats: torch.Tensor):
         """All convolutions for a built pyramid: no host synchronisation, no allocation outside torch's caching allocator."""
+        if self.trainable and self.training:
+            return self._run_train(pyr, feats)
         if self.training or any(m.training for m in self.modules()):
             raise NotImplementedError("Res16UNet34C on the HIP kernels runs in eval mode only (frozen backbone)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -379,6 +584,154 @@ class Res16UNet34C(nn.Module):
         f1 = block(8, cat8, 0)
         out = f1.index_select(0, pyr.inv)      # res16unet.py:307-314: the forward returns block8's output; `final` is never applied
         return out, [f16, f8, f4, f2, out]
+
+    # ---- training: batch-statistics BatchNorm, one autograd node for the whole network
+    def unused_parameters(self):
+        """``final.*`` when trainable: the forward never applies ``final`` (as the reference's), so it never gets a gradient."""
+        return list(self.final.parameters()) if self.trainable else []
+
+    def _layers(self):
+        """[(name, conv, norm)] of every convolution the forward runs, in forward order (``final`` is not one of them)."""
+        out = [("conv0p1s1", self.conv0p1s1, self.bn0)]
+        for i, name in enumerate(("conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")):
+            out.append((name, getattr(self, name), getattr(self, f"bn{i + 1}")))
+        for i, name in enumerate(("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")):
+            out.append((name, getattr(self, name), getattr(self, f"bntr{4 + i}")))
+        for bi in range(1, 9):
+            for j, blk in enumerate(getattr(self, f"block{bi}")):
+                out.append((f"block{bi}.{j}.conv1", blk.conv1, blk.norm1))
+                out.append((f"block{bi}.{j}.conv2", blk.conv2, blk.norm2))
+                if blk.downsample is not None:
+                    out.append((f"block{bi}.{j}.downsample", blk.downsample[0], blk.downsample[1]))
+        return out
+
+    def _run_train(self, pyr: CoordPyramid, feats: torch.Tensor):
+        if not feats.is_cuda:
+            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+        assert feats.shape == (pyr.N, self.conv0p1s1.cin), "feats is [N, in_channels] in the row order of the coordinates"
+        layers = self._layers()
+        params = [p for _n, conv, norm in layers for p in (conv.kernel, norm.bn.weight, norm.bn.bias)]
+        f16, f8, f4, f2, out = _BackboneTrain.apply(self, pyr, layers, feats.detach().float(), *params)
+        return out, [f16, f8, f4, f2, out]
+
+    def training_tape(self, pyr: CoordPyramid, feats: torch.Tensor):
+        """One training-mode forward outside autograd (the running buffers ARE updated): ``{layer name: (conv, norm, record)}``
+        with the record the backward works from -- ``x`` the layer's input, ``kmap`` its kernel map (None for the 1 x 1
+        ``downsample``), ``z`` the raw convolution output, ``y`` the activation, ``mean`` / ``rstd`` the batch statistics.
+        For tools that time or inspect single layers."""
+        layers, tape = self._layers(), {}
+        with torch.no_grad():
+            self._train_forward(pyr, feats.detach().float(), layers, tape)
+        return {name: (conv, norm, tape[name]) for name, conv, norm in layers}
+
+    def _train_forward(self, pyr, feats, layers, tape):
+        """Convolution (raw fp32 weights, converted in the kernel) -> batch statistics -> normalise for every layer; ``tape``
+        receives, per layer name, what the backward needs: the input, the raw output z, the activation y, mean and rstd."""
+        ct, n, dev = self.ct, pyr.n, feats.device
+        PL, I = self.PLANES, self.INIT_DIM
+        mods = {name: (conv, norm) for name, conv, norm in layers}
+        new = lambda rows, c: torch.empty(rows, c, dtype=torch.float32, device=dev)
+
+        def cbr(name, x, kmap, residual=None, act="relu", out=None, col_off=0):
+            conv, norm = mods[name]
+            bn = norm.bn
+            z = sparse_conv(x, kmap, conv.kernel.detach(), ct=ct) if conv.K > 1 else _gemm_raw(x, conv.kernel.detach(), ct)
+            mean, rstd = bn_stats(z, bn.eps, bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            y = bn_apply(z, mean, rstd, bn.weight.detach(), bn.bias.detach(), residual=residual, act=act, out=out, col_off=col_off)
+            tape[name] = dict(x=x, kmap=kmap, z=z, y=y, mean=mean, rstd=rstd, act=act)
+            return y
+
+        def block(bi, x, l, out=None, col_off=0):
+            blocks = getattr(self, f"block{bi}")
+            for j, blk in enumerate(blocks):
+                name = f"block{bi}.{j}"
+                last = j == len(blocks) - 1
+                y = cbr(name + ".conv1", x, pyr.nbr3[l])
+                res = cbr(name + ".downsample", x, None, act=None) if blk.downsample is not None else x
+                x = cbr(name + ".conv2", y, pyr.nbr3[l], residual=res, out=out if last else None, col_off=col_off if last else 0)
+            return x
+
+        cat8, cat7 = new(n[0], PL[7] + I), new(n[1], PL[6] + PL[0])
+        cat6, cat5 = new(n[2], PL[5] + PL[1]), new(n[3], PL[4] + PL[2])
+        x0 = feats.index_select(0, pyr.perm)
+        out_p1 = cbr("conv0p1s1", x0, pyr.nbr5 if self.conv0p1s1.K == 125 else pyr.nbr3[0], out=cat8, col_off=PL[7])
+        b1 = block(1, cbr("conv1p1s2", out_p1, pyr.down[0]), 1, out=cat7, col_off=PL[6])
+        b2 = block(2, cbr("conv2p2s2", b1, pyr.down[1]), 2, out=cat6, col_off=PL[5])
+        b3 = block(3, cbr("conv3p4s2", b2, pyr.down[2]), 3, out=cat5, col_off=PL[4])
+        f16 = block(4, cbr("conv4p8s2", b3, pyr.down[3]), 4)
+        cbr("convtr4p16s2", f16, pyr.up[3], out=cat5)
+        f8 = block(5, cat5, 3)
+        cbr("convtr5p8s2", f8, pyr.up[2], out=cat6)
+        f4 = block(6, cat6, 2)
+        cbr("convtr6p4s2", f4, pyr.up[1], out=cat7)
+        f2 = block(7, cat7, 1)
+        cbr("convtr7p2s2", f2, pyr.up[0], out=cat8)
+        f1 = block(8, cat8, 0)
+        return f16, f8, f4, f2, f1.index_select(0, pyr.inv)
+
+    def _train_backward(self, pyr, layers, tape, g16, g8, g4, g2, gout):
+        """The tape walked in reverse.  Returns {layer name: (dkernel, dbn.weight, dbn.bias)}.  The gradient of a concatenation is
+        one buffer whose halves are read as strided views; a tensor with two consumers (block input and skip connection, a
+        feature map that is also an output) gets the second gradient through the input-gradient kernel's ``residual``."""
+        ct, PL = self.ct, self.PLANES
+        mods = {name: (conv, norm) for name, conv, norm in layers}
+        grads = {}
+
+        def bn_back(name, dy, dres=None):
+            """dz of layer ``name`` from the gradient of its activation; records the BatchNorm parameter gradients."""
+            (_conv, norm), t = mods[name], tape[name]
+            y = t["y"] if t["act"] else None
+            dg, db = bn_bwd_reduce(dy, t["z"], t["mean"], t["rstd"], y=y)
+            dz = bn_bwd_apply(dy, t["z"], t["mean"], t["rstd"], norm.bn.weight.detach(), dg, db, y=y, dres=dres)
+            grads[name] = [None, dg, db]
+            return dz
+
+        def conv_back(name, dz, kmap_t, reverse_k, residual=None, need_dx=True):
+            """Weight gradient of layer ``name`` (recorded) and the gradient of its input (+ residual)."""
+            (conv, _norm), t = mods[name], tape[name]
+            grads[name][0] = sparse_conv_bwd_weight(t["x"], t["kmap"], dz, ct=ct)
+            return sparse_conv_bwd_input(dz, kmap_t, conv.kernel.detach(), reverse_k, ct=ct, residual=residual) if need_dx else None
+
+        def block_back(bi, l, d):
+            """``d``: gradient of block group ``bi``'s output -> gradient of its input."""
+            blocks = getattr(self, f"block{bi}")
+            for j in reversed(range(len(blocks))):
+                name = f"block{bi}.{j}"
+                g = torch.empty(d.shape[0], d.shape[1], dtype=torch.float32, device=d.device)   # the residual branch's gradient
+                dz2 = bn_back(name + ".conv2", d, dres=g)
+                dy1 = conv_back(name + ".conv2", dz2, pyr.nbr3[l], True)
+                dz1 = bn_back(name + ".conv1", dy1)
+                if blocks[j].downsample is not None:
+                    dn = name + ".downsample"
+                    dzd = bn_back(dn, g)
+                    g, grads[dn][0] = _gemm_raw_bwd(tape[dn]["x"], mods[dn][0].kernel.detach(), dzd, ct)
+                d = conv_back(name + ".conv1", dz1, pyr.nbr3[l], True, residual=g)
+            return d
+
+        def up_back(name, dcat, l, g_ext):
+            """transposed convolution level l + 1 -> l whose output is the left half of ``dcat``'s buffer"""
+            dz = bn_back(name, dcat[:, :mods[name][0].cout])
+            return conv_back(name, dz, pyr.down[l], False, residual=g_ext)
+
+        def down_back(name, d, l, dskip):
+            """stride-2 convolution level l -> l + 1 whose input is also the skip connection with gradient ``dskip``"""
+            return conv_back(name, bn_back(name, d), pyr.up[l], False, residual=dskip)
+
+        if gout is None:
+            d = torch.zeros(pyr.N, PL[7], dtype=torch.float32, device=pyr.device)
+        else:
+            d = gout.float().index_select(0, pyr.perm)            # out = f1[inv]  =>  df1 = dout[perm]
+        dcat8 = block_back(8, 0, d)
+        dcat7 = block_back(7, 1, up_back("convtr7p2s2", dcat8, 0, g2))
+        dcat6 = block_back(6, 2, up_back("convtr6p4s2", dcat7, 1, g4))
+        dcat5 = block_back(5, 3, up_back("convtr5p8s2", dcat6, 2, g8))
+        d = block_back(4, 4, up_back("convtr4p16s2", dcat5, 3, g16))
+        d = block_back(3, 3, down_back("conv4p8s2", d, 3, dcat5[:, PL[4]:]))
+        d = block_back(2, 2, down_back("conv3p4s2", d, 2, dcat6[:, PL[5]:]))
+        d = block_back(1, 1, down_back("conv2p2s2", d, 1, dcat7[:, PL[6]:]))
+        d = down_back("conv1p1s2", d, 0, dcat8[:, PL[7]:])
+        conv_back("conv0p1s1", bn_back("conv0p1s1", d), None, False, need_dx=False)   # feats never requires grad
+        return grads
 
     def forward(self, coords: torch.Tensor, feats: torch.Tensor):
         out, maps = self.run(CoordPyramid(coords), feats)

@@ -13,7 +13,12 @@ voxels (synth.instseg_room: V voxels per scene), B = 1 and B = 4, compute 'fp32'
   torch_*     baseline: the textbook gather -> matmul -> index_add_ loop over the kernel offsets in stock torch on the same
               GPU, same inputs, same maps (index lists prepared outside the timed window), BatchNorm / residual / ReLU as
               separate torch ops -- there is no MinkowskiEngine for this GPU to compare with
-Prints one JSON line.    python tools/bench_voxel_backbone.py [--V 100000 --iters 30 --torch-iters 8]"""
+--train times forward + backward of the TRAINABLE network instead (batch-statistics BatchNorm, sparse-convolution backward):
+  fwd_bwd_ms / torch_fwd_bwd_ms  one training forward + backward, ours and the same torch loop under torch autograd with
+              batch_norm in training mode; [min, median, max] by the same device-event method
+  classes     (B = 4) calls and ms of ours per class of launch (forward convolution, input gradient, weight gradient, BatchNorm,
+              1 x 1 GEMM) and torch_ms: the torch loop's time for the same class of work on the same tensors
+Prints one JSON line.    python tools/bench_voxel_backbone.py [--train] [--V 100000 --iters 30 --torch-iters 8]"""
 import argparse, json, os, re, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -90,6 +95,138 @@ class TorchLoop:
         return self._timed(("gemm", x.shape[0], x.shape[0], 1), run)
 
 
+def torch_train_step(model, pyr, feats, tl, Rs):
+    """Forward + backward of the TRAINING network in stock torch under autograd: the gather -> matmul -> index_add loop per
+    offset, nn.functional.batch_norm in training mode (on copies of the running buffers), ReLU, torch.cat.  Returns the
+    parameter gradients."""
+    import torch.nn.functional as F
+    ct = model.ct
+    dt = torch.bfloat16 if ct == 1 else torch.float32
+    params = []
+
+    def pairs_of(kmap):
+        if id(kmap) not in tl.pairs:
+            tl.pairs[id(kmap)] = [((kmap.nbr[:, k] >= 0).nonzero()[:, 0], kmap.nbr[:, k][kmap.nbr[:, k] >= 0].long()) for k in range(kmap.K)]
+        return tl.pairs[id(kmap)]
+
+    def cbr(conv, norm, x, kmap, residual=None, act=True):
+        W, bn = conv.kernel, norm.bn
+        params.extend([W, bn.weight, bn.bias])
+        if conv.K == 1:
+            z = (x.to(dt) @ W.to(dt)).float()
+        else:
+            z, xs = torch.zeros(kmap.n_out, conv.cout, device=x.device), x.to(dt)
+            for k, (o, i) in enumerate(pairs_of(kmap)):
+                if o.numel():
+                    z.index_add_(0, o, (xs[i] @ W[k].to(dt)).float())
+        y = F.batch_norm(z, bn.running_mean.clone(), bn.running_var.clone(), bn.weight, bn.bias, True, bn.momentum, bn.eps)
+        if residual is not None:
+            y = y + residual
+        return torch.relu(y) if act else y
+
+    def block(bi, x, l):
+        for blk in getattr(model, f"block{bi}"):
+            y = cbr(blk.conv1, blk.norm1, x, pyr.nbr3[l])
+            res = cbr(blk.downsample[0], blk.downsample[1], x, None, act=False) if blk.downsample is not None else x
+            x = cbr(blk.conv2, blk.norm2, y, pyr.nbr3[l], residual=res)
+        return x
+
+    x = cbr(model.conv0p1s1, model.bn0, feats.index_select(0, pyr.perm), pyr.nbr5 if model.conv0p1s1.K == 125 else pyr.nbr3[0])
+    skip = [x]
+    for i, name in enumerate(("conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")):
+        x = block(i + 1, cbr(getattr(model, name), getattr(model, f"bn{i + 1}"), x, pyr.down[i]), i + 1)
+        skip.append(x)
+    maps = [x]
+    for i, name in enumerate(("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")):
+        l = 3 - i
+        x = cbr(getattr(model, name), getattr(model, f"bntr{4 + i}"), x, pyr.up[l])
+        x = block(5 + i, torch.cat([x, skip[l]], 1), l)
+        maps.append(x)
+    maps[4] = maps[4].index_select(0, pyr.inv)
+    return torch.autograd.grad(sum((m * r).sum() for m, r in zip(maps, Rs)), params)
+
+
+def train_leg(a, out):
+    """--train: forward + backward ms of Res16UNet34C(trainable=True).train() against the stock-torch loop under autograd, B = 1
+    and 4, both compute modes; at B = 4 a per-class split of ours (KernelTimer around one step) next to the torch loop's time
+    for the same class of work, measured operator by operator on the tensors of our tape (the median of --torch-iters event pairs after 3 warm-up calls around: the gather ->
+    matmul -> index_add input gradient, the per-offset x^T dy weight gradient, batch_norm forward + backward through autograd)."""
+    import torch.nn.functional as F
+    model = sparse.Res16UNet34C(3, a.out_channels, {"bn_momentum": 0.02, "conv1_kernel_size": 5}, trainable=True)
+    synth.fill_module(model, 0)
+    for m in model.modules():
+        if isinstance(m, torch.nn.BatchNorm1d):
+            m.running_var.copy_(m.running_var.abs() + 0.5)
+    model.cuda().train()
+    params = [p for n, p in model.named_parameters() if not n.startswith("final")]
+    for B in (1, 4):
+        coords = room_coords(B, a.V).cuda()
+        feats = torch.rand(coords.shape[0], 3, device="cuda")
+        pyr = sparse.CoordPyramid(coords)
+        g = torch.Generator(device="cuda").manual_seed(3)
+        Rs = [torch.randn(pyr.n[4 - h], c, device="cuda", generator=g) for h, c in enumerate((256, 256, 128, 96, 96))]
+        res = dict(voxels=int(coords.shape[0]), level_rows=pyr.n)
+
+        def ours():
+            _o, maps = model.run(pyr, feats)
+            return torch.autograd.grad(sum((m * r).sum() for m, r in zip(maps, Rs)), params)
+
+        for compute in ("fp32", "bf16"):
+            model.compute = compute
+            total = events(ours, a.iters)
+            tl = TorchLoop()
+            torch_total = events(lambda: torch_train_step(model, pyr, feats, tl, Rs), a.torch_iters)
+            go, gt = ours(), torch_train_step(model, pyr, feats, tl, Rs)
+            grad_norm = float(torch.cat([x.flatten() for x in go]).norm())      # (the two steps list their parameters in different orders)
+            r = dict(fwd_bwd_ms=total, torch_fwd_bwd_ms=torch_total, speedup=round(torch_total[1] / total[1], 2), grad_norm=float(f"{grad_norm:.4g}"),
+                     torch_grad_norm=float(f"{float(torch.cat([x.flatten() for x in gt]).norm()):.4g}"))
+            if B == 4:
+                with KernelTimer() as kt:
+                    ours()
+                cls = {}
+                for (name, key), v in kt.summary().items():
+                    c = ("input_gradient" if re.search(r"w[12]$", key) else "forward_conv") if name == "pq3d_sparse_conv_fwd" else \
+                        "weight_gradient" if name == "pq3d_sparse_conv_wgrad" else "batchnorm" if name.startswith("pq3d_bn_") else \
+                        "1x1_gemm" if name == "pq3d_gemm" else name
+                    e = cls.setdefault(c, dict(calls=0, ms=0.0))
+                    e["calls"] += v["calls"]; e["ms"] += v["ms"]
+                dt = torch.bfloat16 if compute == "bf16" else torch.float32
+                tms = dict(input_gradient=0.0, weight_gradient=0.0, batchnorm=0.0)
+
+                def timed(key, fn):      # the tool's method per operator: 3 warm-up calls, then the median of --torch-iters
+                    tms[key] += events(fn, a.torch_iters)[1]
+                for lname, (conv, norm, t) in model.training_tape(pyr, feats).items():
+                    z, bn = t["z"], norm.bn
+                    dy = torch.randn_like(z)
+
+                    def bn_fb():
+                        zz = z.detach().requires_grad_(True)
+                        y = torch.relu(F.batch_norm(zz, bn.running_mean.clone(), bn.running_var.clone(), bn.weight, bn.bias, True, bn.momentum, bn.eps))
+                        torch.autograd.grad(y, (zz, bn.weight, bn.bias), dy)
+                    timed("batchnorm", bn_fb)
+                    if conv.K == 1:
+                        continue
+                    x, W, prs = t["x"], conv.kernel.detach(), [(o, i) for o, i in tl.pairs[id(t["kmap"])] if o.numel()]
+                    ks = [k for k, (o, i) in enumerate(tl.pairs[id(t["kmap"])]) if o.numel()]
+
+                    def dx():
+                        acc, d = torch.zeros(x.shape[0], x.shape[1], device="cuda"), dy.to(dt)
+                        for k, (o, i) in zip(ks, prs):
+                            acc.index_add_(0, i, (d[o] @ W[k].to(dt).t()).float())
+
+                    def dw():
+                        xs, d, gw = x.to(dt), dy.to(dt), torch.zeros_like(W)
+                        for k, (o, i) in zip(ks, prs):
+                            gw[k] = (xs[i].t() @ d[o]).float()
+                    if lname != "conv0p1s1":
+                        timed("input_gradient", dx)
+                    timed("weight_gradient", dw)
+                r["classes"] = {k: dict(calls=v["calls"], ms=round(v["ms"], 3), torch_ms=round(tms[k], 3) if k in tms else None)
+                                for k, v in sorted(cls.items())}
+            res[compute] = r
+        out[f"train_B{B}"] = res
+
+
 def class_of(n, n_out, n_in, K):
     lvl = f"s{1 << n.index(n_out)}" if n_out in n else f"n{n_out}"
     kind = {125: "stem5", 27: "conv3", 1: "1x1"}.get(K) or ("down2" if n_out < n_in else "up2")
@@ -101,8 +238,14 @@ def main():
     ap.add_argument("--V", type=int, default=100_000); ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--torch-iters", type=int, default=8)
     ap.add_argument("--map-iters", type=int, default=5); ap.add_argument("--out-channels", type=int, default=200)
+    ap.add_argument("--train", action="store_true", help="time forward + backward of the trainable network instead")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_voxel_backbone.py needs a GPU"
+    if a.train:
+        out = dict(metric="voxel_backbone_train", V=a.V, out_channels=a.out_channels)
+        train_leg(a, out)
+        print(json.dumps(out))
+        return
     model = sparse.Res16UNet34C(3, a.out_channels, {"bn_momentum": 0.02, "conv1_kernel_size": 5})
     synth.fill_module(model, 0)
     model.cuda()

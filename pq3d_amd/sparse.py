@@ -368,12 +368,12 @@ class BasicBlock(nn.Module):
 
 class _BackboneTrain(torch.autograd.Function):
     """Res16UNet34C's training forward and backward as ONE autograd node: inputs are every kernel / bn.weight / bn.bias in
-    ``layers`` order, outputs the five feature maps."""
+    the order of the network's layer table, outputs the five feature maps."""
 
     @staticmethod
-    def forward(ctx, net, pyr, layers, feats, *params):
+    def forward(ctx, net, pyr, feats, *params):
         tape = {}
-        outs = net._train_forward(pyr, feats, layers, tape)
+        outs = net._train_forward(pyr, feats, tape)
         # the coarse maps are outputs AND tape entries (the ReLU mask of their own layer, the input of the next transposed
         # convolution): those go through save_for_backward.  An output kept as a plain attribute ties the node to its own
         # result -- the graph, with the parameters' AccumulateGrad nodes of the stream it ran on, would outlive the step.
@@ -384,7 +384,7 @@ class _BackboneTrain(torch.autograd.Function):
                     t[key] = pos[id(t[key])]
         assert sum(isinstance(t[key], int) for t in tape.values() for key in ("x", "y")) == 8
         ctx.save_for_backward(*outs[:4])
-        ctx.net, ctx.pyr, ctx.layers, ctx.tape = net, pyr, layers, tape
+        ctx.net, ctx.pyr, ctx.tape = net, pyr, tape
         ctx.set_materialize_grads(False)
         return outs
 
@@ -397,9 +397,9 @@ class _BackboneTrain(torch.autograd.Function):
                 if isinstance(t[key], int):
                     t[key] = saved[t[key]]
         cg = lambda g: None if g is None else g.float().contiguous()
-        grads = ctx.net._train_backward(ctx.pyr, ctx.layers, tape, cg(g16), cg(g8), cg(g4), cg(g2), gout)
-        flat = [g for name, _c, _n in ctx.layers for g in grads[name]]
-        return (None, None, None, None, *flat)
+        grads = ctx.net._train_backward(ctx.pyr, tape, cg(g16), cg(g8), cg(g4), cg(g2), gout)
+        flat = [g for name, _c, _n in ctx.net._layers for g in grads[name]]
+        return (None, None, None, *flat)
 
 
 class Res16UNet34C(nn.Module):
@@ -431,6 +431,16 @@ class Res16UNet34C(nn.Module):
     PLANES = (32, 64, 128, 256, 256, 128, 96, 96)
     LAYERS = (2, 3, 4, 6, 2, 2, 2, 2)
     INIT_DIM = 32
+    # The U-Net's graph below the stem.  Down stage i takes level i to level i + 1 (tensor stride 2^(i+1)): (stride-2 convolution,
+    # its BatchNorm, the block group that follows; planes PLANES[i]).  Up stage i takes level 4 - i to level 3 - i: (transposed
+    # convolution, its BatchNorm, the block group that runs on [its output | skip]; planes PLANES[4 + i], width of that skip).
+    _DOWN = (("conv1p1s2", "bn1", "block1"), ("conv2p2s2", "bn2", "block2"),
+             ("conv3p4s2", "bn3", "block3"), ("conv4p8s2", "bn4", "block4"))
+    _UP = (("convtr4p16s2", "bntr4", "block5", PLANES[2]), ("convtr5p8s2", "bntr5", "block6", PLANES[1]),
+           ("convtr6p4s2", "bntr6", "block7", PLANES[0]), ("convtr7p2s2", "bntr7", "block8", INIT_DIM))
+    # (left, skip) widths of the concatenation buffer of level l = 0..3, the one up stage 3 - l fills: the forward writes the
+    # skip at column `left`, the backward splits the buffer's gradient there
+    _CAT = tuple(zip(PLANES[4:], (stage[3] for stage in _UP)))[::-1]
 
     def __init__(self, in_channels: int, out_channels: int, config, out_fpn: bool = True, D: int = 3, compute: str = "fp32",
                  trainable: bool = False):
@@ -443,19 +453,31 @@ class Res16UNet34C(nn.Module):
         self.conv0p1s1 = SparseConv(in_channels, self.inplanes, int(config["conv1_kernel_size"]))
         assert self.conv0p1s1.K in (27, 125), "conv1_kernel_size 3 or 5"
         self.bn0 = SparseBatchNorm(self.inplanes, mom)
-        for i, name in enumerate(("conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")):
-            setattr(self, name, SparseConv(self.inplanes, self.inplanes, 2))
-            setattr(self, f"bn{i + 1}", SparseBatchNorm(self.inplanes, mom))
-            setattr(self, f"block{i + 1}", self._make_layer(P[i], self.LAYERS[i], mom))
-        skips = (P[2], P[1], P[0], self.INIT_DIM)
-        for i, name in enumerate(("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")):
-            setattr(self, name, SparseConv(self.inplanes, P[4 + i], 2))
-            setattr(self, f"bntr{4 + i}", SparseBatchNorm(P[4 + i], mom))
-            self.inplanes = P[4 + i] + skips[i]
-            setattr(self, f"block{5 + i}", self._make_layer(P[4 + i], self.LAYERS[4 + i], mom))
+        for i, (conv, bn, group) in enumerate(self._DOWN):
+            setattr(self, conv, SparseConv(self.inplanes, self.inplanes, 2))
+            setattr(self, bn, SparseBatchNorm(self.inplanes, mom))
+            setattr(self, group, self._make_layer(P[i], self.LAYERS[i], mom))
+        for i, (conv, bn, group, skip) in enumerate(self._UP):
+            setattr(self, conv, SparseConv(self.inplanes, P[4 + i], 2))
+            setattr(self, bn, SparseBatchNorm(P[4 + i], mom))
+            self.inplanes = P[4 + i] + skip
+            setattr(self, group, self._make_layer(P[4 + i], self.LAYERS[4 + i], mom))
         self.final = SparseConv(P[7], out_channels, 1, bias=True)
         del self.inplanes
         self._prep = None
+        # every (name, convolution, BatchNorm) the forward runs, in the order of the training node's inputs and gradients
+        # (``final`` is not one of them), and the names of each group's blocks.  Plain containers of MODULES: nn.Module does not
+        # register them a second time, and whatever replaces a parameter or its data leaves them valid.
+        stages = self._DOWN + self._UP
+        self._layers = [(conv, getattr(self, conv), getattr(self, bn)) for conv, bn, *_ in (("conv0p1s1", "bn0"),) + stages]
+        self._blocks = {}
+        for group in (s[2] for s in stages):
+            self._blocks[group] = [f"{group}.{j}" for j in range(len(getattr(self, group)))]
+            for name, blk in zip(self._blocks[group], getattr(self, group)):
+                self._layers += [(name + ".conv1", blk.conv1, blk.norm1), (name + ".conv2", blk.conv2, blk.norm2)]
+                if blk.downsample is not None:
+                    self._layers.append((name + ".downsample", blk.downsample[0], blk.downsample[1]))
+        self._by_name = {name: (conv, norm) for name, conv, norm in self._layers}
         if self.trainable:
             return                      # parameters require grad, training mode: as any freshly built module
         self.requires_grad_(False)
@@ -507,132 +529,101 @@ class Res16UNet34C(nn.Module):
             s = (bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps))
             return s.float().contiguous(), (bn.bias.detach().double() - bn.running_mean.double() * s).float().contiguous()
 
-        def add(name, conv, norm):
-            scale, shift = fold(norm) if norm is not None else (None, None)
+        for name, conv, norm in self._layers:
+            scale, shift = fold(norm)
             w = conv.kernel.detach()
             if conv.K == 1:     # row GEMM: the scale goes into the weight (fp32, before the conversion), the shift is the bias
                 P[name] = ((w * scale[None, :]).t().to(wdt).contiguous(), shift)
             else:
                 P[name] = (w.to(wdt).contiguous(), scale, shift)
-        for i, name in enumerate(("conv0p1s1", "conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")):
-            add(name, getattr(self, name), getattr(self, f"bn{i}"))
-        for i, name in enumerate(("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")):
-            add(name, getattr(self, name), getattr(self, f"bntr{4 + i}"))
-        for bi in range(1, 9):
-            for j, blk in enumerate(getattr(self, f"block{bi}")):
-                add(f"block{bi}.{j}.conv1", blk.conv1, blk.norm1)
-                add(f"block{bi}.{j}.conv2", blk.conv2, blk.norm2)
-                if blk.downsample is not None:
-                    add(f"block{bi}.{j}.downsample", blk.downsample[0], blk.downsample[1])
         self._prep = P
         return P
 
     # ---- the launches (capturable)
     def run(self, pyr: CoordPyramid, feats: torch.Tensor):
         """All convolutions for a built pyramid: no host synchronisation, no allocation outside torch's caching allocator."""
-        if self.trainable and self.training:
-            return self._run_train(pyr, feats)
-        if self.training or any(m.training for m in self.modules()):
-            raise NotImplementedError("Res16UNet34C on the HIP kernels runs in eval mode only (frozen backbone)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("training the voxel backbone is not provided: call under torch.no_grad() "
-                                      "(freeze_backbone=True) or set requires_grad_(False)")
+        train = self.trainable and self.training
+        if not train:
+            if self.training or any(m.training for m in self.modules()):
+                raise NotImplementedError("Res16UNet34C on the HIP kernels runs in eval mode only (frozen backbone)")
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                raise NotImplementedError("training the voxel backbone is not provided: call under torch.no_grad() "
+                                          "(freeze_backbone=True) or set requires_grad_(False)")
         if not feats.is_cuda:
             raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
         assert feats.shape == (pyr.N, self.conv0p1s1.cin), "feats is [N, in_channels] in the row order of the coordinates"
+        feats = feats.detach().float()
+        if train:
+            params = [p for _name, conv, norm in self._layers for p in (conv.kernel, norm.bn.weight, norm.bn.bias)]
+            maps = list(_BackboneTrain.apply(self, pyr, feats, *params))
+            return maps[4], maps
         with torch.no_grad():
-            return self._run(pyr, feats.detach().float())
+            return self._run(pyr, feats)
 
-    def _run(self, pyr, feats):
-        P, ct, n, dev = self.prepare(), self.ct, pyr.n, feats.device
-        PL, I = self.PLANES, self.INIT_DIM
-        new = lambda rows, c: torch.empty(rows, c, dtype=torch.float32, device=dev)
+    def _walk(self, pyr, feats, layer):
+        """The network's graph, for both modes: the five feature maps (strides 16, 8, 4, 2, 1; the last in the caller's row order).
+        ``layer(name, x, kmap, residual=None, act="relu", out=None, col_off=0)`` executes one named layer (``kmap`` None: the
+        1 x 1 ``downsample``) and returns its activation, the [rows, Cout] column view of ``out`` at ``col_off``."""
+        # (concatenation buffer [transposed-convolution output | skip], column of the skip) of levels 0..3.  Both halves are
+        # written where they are produced: the skip by the way down's last layer at that level.
+        cat = [(torch.empty(pyr.n[l], left + skip, dtype=torch.float32, device=feats.device), left)
+               for l, (left, skip) in enumerate(self._CAT)]
 
-        def conv(name, x, kmap, residual=None, out=None, col_off=0):
-            W, scale, shift = P[name]
-            return sparse_conv(x, kmap, W, ct=ct, scale=scale, shift=shift, residual=residual, act="relu", out=out, col_off=col_off)
-
-        def block(bi, x, l, out=None, col_off=0):
-            blocks = getattr(self, f"block{bi}")
-            for j, blk in enumerate(blocks):
-                name = f"block{bi}.{j}"
-                last = j == len(blocks) - 1
-                y = conv(name + ".conv1", x, pyr.nbr3[l])
-                res = row_gemm(x, *P[name + ".downsample"], ct) if blk.downsample is not None else x
-                x = conv(name + ".conv2", y, pyr.nbr3[l], residual=res, out=out if last else None, col_off=col_off if last else 0)
-                if last and out is not None:
-                    x = out[:, col_off:col_off + blk.conv2.cout]
+        def blocks(group, x, l, out=None, col_off=0):
+            names = self._blocks[group]
+            for j, name in enumerate(names):
+                last = j == len(names) - 1
+                y = layer(name + ".conv1", x, pyr.nbr3[l])
+                res = layer(name + ".downsample", x, None, act=None) if name + ".downsample" in self._by_name else x
+                x = layer(name + ".conv2", y, pyr.nbr3[l], residual=res, out=out if last else None, col_off=col_off if last else 0)
             return x
 
-        # the four concatenation buffers [transposed-convolution output | skip]: both halves are written where they are produced
-        cat8, cat7 = new(n[0], PL[7] + I), new(n[1], PL[6] + PL[0])
-        cat6, cat5 = new(n[2], PL[5] + PL[1]), new(n[3], PL[4] + PL[2])
-        x0 = feats.index_select(0, pyr.perm)
-        conv("conv0p1s1", x0, pyr.nbr5 if self.conv0p1s1.K == 125 else pyr.nbr3[0], out=cat8, col_off=PL[7])
-        out_p1 = cat8[:, PL[7]:]
-        b1 = block(1, conv("conv1p1s2", out_p1, pyr.down[0]), 1, out=cat7, col_off=PL[6])
-        b2 = block(2, conv("conv2p2s2", b1, pyr.down[1]), 2, out=cat6, col_off=PL[5])
-        b3 = block(3, conv("conv3p4s2", b2, pyr.down[2]), 3, out=cat5, col_off=PL[4])
-        f16 = block(4, conv("conv4p8s2", b3, pyr.down[3]), 4)
-        conv("convtr4p16s2", f16, pyr.up[3], out=cat5)
-        f8 = block(5, cat5, 3)
-        conv("convtr5p8s2", f8, pyr.up[2], out=cat6)
-        f4 = block(6, cat6, 2)
-        conv("convtr6p4s2", f4, pyr.up[1], out=cat7)
-        f2 = block(7, cat7, 1)
-        conv("convtr7p2s2", f2, pyr.up[0], out=cat8)
-        f1 = block(8, cat8, 0)
-        out = f1.index_select(0, pyr.inv)      # res16unet.py:307-314: the forward returns block8's output; `final` is never applied
-        return out, [f16, f8, f4, f2, out]
+        out, col_off = cat[0]
+        x = layer("conv0p1s1", feats.index_select(0, pyr.perm), pyr.nbr5 if self.conv0p1s1.K == 125 else pyr.nbr3[0], out=out, col_off=col_off)
+        for l, (conv, _bn, group) in enumerate(self._DOWN, 1):
+            out, col_off = cat[l] if l < 4 else (None, 0)      # the coarsest level feeds no skip
+            x = blocks(group, layer(conv, x, pyr.down[l - 1]), l, out, col_off)
+        maps = [x]
+        for l, (conv, _bn, group, _skip) in zip((3, 2, 1, 0), self._UP):
+            layer(conv, x, pyr.up[l], out=cat[l][0])
+            x = blocks(group, cat[l][0], l)
+            maps.append(x)
+        maps[4] = x.index_select(0, pyr.inv)   # res16unet.py:307-314: the forward returns block8's output; `final` is never applied
+        return maps
+
+    def _run(self, pyr, feats):
+        P, ct = self.prepare(), self.ct
+
+        def layer(name, x, kmap, residual=None, act="relu", out=None, col_off=0):
+            if kmap is None:
+                return row_gemm(x, *P[name], ct, act)
+            W, scale, shift = P[name]
+            y = sparse_conv(x, kmap, W, ct=ct, scale=scale, shift=shift, residual=residual, act=act, out=out, col_off=col_off)
+            return y if out is None else y[:, col_off:col_off + W.shape[2]]      # sparse_conv returns the whole buffer
+        maps = self._walk(pyr, feats, layer)
+        return maps[4], maps
 
     # ---- training: batch-statistics BatchNorm, one autograd node for the whole network
     def unused_parameters(self):
         """``final.*`` when trainable: the forward never applies ``final`` (as the reference's), so it never gets a gradient."""
         return list(self.final.parameters()) if self.trainable else []
 
-    def _layers(self):
-        """[(name, conv, norm)] of every convolution the forward runs, in forward order (``final`` is not one of them)."""
-        out = [("conv0p1s1", self.conv0p1s1, self.bn0)]
-        for i, name in enumerate(("conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")):
-            out.append((name, getattr(self, name), getattr(self, f"bn{i + 1}")))
-        for i, name in enumerate(("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")):
-            out.append((name, getattr(self, name), getattr(self, f"bntr{4 + i}")))
-        for bi in range(1, 9):
-            for j, blk in enumerate(getattr(self, f"block{bi}")):
-                out.append((f"block{bi}.{j}.conv1", blk.conv1, blk.norm1))
-                out.append((f"block{bi}.{j}.conv2", blk.conv2, blk.norm2))
-                if blk.downsample is not None:
-                    out.append((f"block{bi}.{j}.downsample", blk.downsample[0], blk.downsample[1]))
-        return out
-
-    def _run_train(self, pyr: CoordPyramid, feats: torch.Tensor):
-        if not feats.is_cuda:
-            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
-        assert feats.shape == (pyr.N, self.conv0p1s1.cin), "feats is [N, in_channels] in the row order of the coordinates"
-        layers = self._layers()
-        params = [p for _n, conv, norm in layers for p in (conv.kernel, norm.bn.weight, norm.bn.bias)]
-        f16, f8, f4, f2, out = _BackboneTrain.apply(self, pyr, layers, feats.detach().float(), *params)
-        return out, [f16, f8, f4, f2, out]
-
     def training_tape(self, pyr: CoordPyramid, feats: torch.Tensor):
         """One training-mode forward outside autograd (the running buffers ARE updated): ``{layer name: (conv, norm, record)}``
         with the record the backward works from -- ``x`` the layer's input, ``kmap`` its kernel map (None for the 1 x 1
         ``downsample``), ``z`` the raw convolution output, ``y`` the activation, ``mean`` / ``rstd`` the batch statistics.
         For tools that time or inspect single layers."""
-        layers, tape = self._layers(), {}
+        tape = {}
         with torch.no_grad():
-            self._train_forward(pyr, feats.detach().float(), layers, tape)
-        return {name: (conv, norm, tape[name]) for name, conv, norm in layers}
+            self._train_forward(pyr, feats.detach().float(), tape)
+        return {name: (conv, norm, tape[name]) for name, conv, norm in self._layers}
 
-    def _train_forward(self, pyr, feats, layers, tape):
+    def _train_forward(self, pyr, feats, tape):
         """Convolution (raw fp32 weights, converted in the kernel) -> batch statistics -> normalise for every layer; ``tape``
         receives, per layer name, what the backward needs: the input, the raw output z, the activation y, mean and rstd."""
-        ct, n, dev = self.ct, pyr.n, feats.device
-        PL, I = self.PLANES, self.INIT_DIM
-        mods = {name: (conv, norm) for name, conv, norm in layers}
-        new = lambda rows, c: torch.empty(rows, c, dtype=torch.float32, device=dev)
+        ct, mods = self.ct, self._by_name
 
-        def cbr(name, x, kmap, residual=None, act="relu", out=None, col_off=0):
+        def layer(name, x, kmap, residual=None, act="relu", out=None, col_off=0):
             conv, norm = mods[name]
             bn = norm.bn
             z = sparse_conv(x, kmap, conv.kernel.detach(), ct=ct) if conv.K > 1 else _gemm_raw(x, conv.kernel.detach(), ct)
@@ -640,41 +631,13 @@ class Res16UNet34C(nn.Module):
             y = bn_apply(z, mean, rstd, bn.weight.detach(), bn.bias.detach(), residual=residual, act=act, out=out, col_off=col_off)
             tape[name] = dict(x=x, kmap=kmap, z=z, y=y, mean=mean, rstd=rstd, act=act)
             return y
+        return tuple(self._walk(pyr, feats, layer))
 
-        def block(bi, x, l, out=None, col_off=0):
-            blocks = getattr(self, f"block{bi}")
-            for j, blk in enumerate(blocks):
-                name = f"block{bi}.{j}"
-                last = j == len(blocks) - 1
-                y = cbr(name + ".conv1", x, pyr.nbr3[l])
-                res = cbr(name + ".downsample", x, None, act=None) if blk.downsample is not None else x
-                x = cbr(name + ".conv2", y, pyr.nbr3[l], residual=res, out=out if last else None, col_off=col_off if last else 0)
-            return x
-
-        cat8, cat7 = new(n[0], PL[7] + I), new(n[1], PL[6] + PL[0])
-        cat6, cat5 = new(n[2], PL[5] + PL[1]), new(n[3], PL[4] + PL[2])
-        x0 = feats.index_select(0, pyr.perm)
-        out_p1 = cbr("conv0p1s1", x0, pyr.nbr5 if self.conv0p1s1.K == 125 else pyr.nbr3[0], out=cat8, col_off=PL[7])
-        b1 = block(1, cbr("conv1p1s2", out_p1, pyr.down[0]), 1, out=cat7, col_off=PL[6])
-        b2 = block(2, cbr("conv2p2s2", b1, pyr.down[1]), 2, out=cat6, col_off=PL[5])
-        b3 = block(3, cbr("conv3p4s2", b2, pyr.down[2]), 3, out=cat5, col_off=PL[4])
-        f16 = block(4, cbr("conv4p8s2", b3, pyr.down[3]), 4)
-        cbr("convtr4p16s2", f16, pyr.up[3], out=cat5)
-        f8 = block(5, cat5, 3)
-        cbr("convtr5p8s2", f8, pyr.up[2], out=cat6)
-        f4 = block(6, cat6, 2)
-        cbr("convtr6p4s2", f4, pyr.up[1], out=cat7)
-        f2 = block(7, cat7, 1)
-        cbr("convtr7p2s2", f2, pyr.up[0], out=cat8)
-        f1 = block(8, cat8, 0)
-        return f16, f8, f4, f2, f1.index_select(0, pyr.inv)
-
-    def _train_backward(self, pyr, layers, tape, g16, g8, g4, g2, gout):
+    def _train_backward(self, pyr, tape, g16, g8, g4, g2, gout):
         """The tape walked in reverse.  Returns {layer name: (dkernel, dbn.weight, dbn.bias)}.  The gradient of a concatenation is
         one buffer whose halves are read as strided views; a tensor with two consumers (block input and skip connection, a
         feature map that is also an output) gets the second gradient through the input-gradient kernel's ``residual``."""
-        ct, PL = self.ct, self.PLANES
-        mods = {name: (conv, norm) for name, conv, norm in layers}
+        ct, mods = self.ct, self._by_name
         grads = {}
 
         def bn_back(name, dy, dres=None):
@@ -692,44 +655,41 @@ class Res16UNet34C(nn.Module):
             grads[name][0] = sparse_conv_bwd_weight(t["x"], t["kmap"], dz, ct=ct)
             return sparse_conv_bwd_input(dz, kmap_t, conv.kernel.detach(), reverse_k, ct=ct, residual=residual) if need_dx else None
 
-        def block_back(bi, l, d):
-            """``d``: gradient of block group ``bi``'s output -> gradient of its input."""
-            blocks = getattr(self, f"block{bi}")
-            for j in reversed(range(len(blocks))):
-                name = f"block{bi}.{j}"
+        def block_back(group, l, d):
+            """``d``: gradient of block group ``group``'s output -> gradient of its input."""
+            for name in reversed(self._blocks[group]):
                 g = torch.empty(d.shape[0], d.shape[1], dtype=torch.float32, device=d.device)   # the residual branch's gradient
                 dz2 = bn_back(name + ".conv2", d, dres=g)
                 dy1 = conv_back(name + ".conv2", dz2, pyr.nbr3[l], True)
                 dz1 = bn_back(name + ".conv1", dy1)
-                if blocks[j].downsample is not None:
-                    dn = name + ".downsample"
+                dn = name + ".downsample"
+                if dn in mods:
                     dzd = bn_back(dn, g)
                     g, grads[dn][0] = _gemm_raw_bwd(tape[dn]["x"], mods[dn][0].kernel.detach(), dzd, ct)
                 d = conv_back(name + ".conv1", dz1, pyr.nbr3[l], True, residual=g)
             return d
 
-        def up_back(name, dcat, l, g_ext):
-            """transposed convolution level l + 1 -> l whose output is the left half of ``dcat``'s buffer"""
-            dz = bn_back(name, dcat[:, :mods[name][0].cout])
-            return conv_back(name, dz, pyr.down[l], False, residual=g_ext)
+        def up_back(name, dcat, left, l, g_ext):
+            """transposed convolution level l + 1 -> l whose output is the ``left`` columns of ``dcat``'s buffer"""
+            return conv_back(name, bn_back(name, dcat[:, :left]), pyr.down[l], False, residual=g_ext)
 
         def down_back(name, d, l, dskip):
             """stride-2 convolution level l -> l + 1 whose input is also the skip connection with gradient ``dskip``"""
             return conv_back(name, bn_back(name, d), pyr.up[l], False, residual=dskip)
 
         if gout is None:
-            d = torch.zeros(pyr.N, PL[7], dtype=torch.float32, device=pyr.device)
+            d = torch.zeros(pyr.N, self.PLANES[7], dtype=torch.float32, device=pyr.device)
         else:
             d = gout.float().index_select(0, pyr.perm)            # out = f1[inv]  =>  df1 = dout[perm]
-        dcat8 = block_back(8, 0, d)
-        dcat7 = block_back(7, 1, up_back("convtr7p2s2", dcat8, 0, g2))
-        dcat6 = block_back(6, 2, up_back("convtr6p4s2", dcat7, 1, g4))
-        dcat5 = block_back(5, 3, up_back("convtr5p8s2", dcat6, 2, g8))
-        d = block_back(4, 4, up_back("convtr4p16s2", dcat5, 3, g16))
-        d = block_back(3, 3, down_back("conv4p8s2", d, 3, dcat5[:, PL[4]:]))
-        d = block_back(2, 2, down_back("conv3p4s2", d, 2, dcat6[:, PL[5]:]))
-        d = block_back(1, 1, down_back("conv2p2s2", d, 1, dcat7[:, PL[6]:]))
-        d = down_back("conv1p1s2", d, 0, dcat8[:, PL[7]:])
+        dskip = []              # by level: the skip half of the concatenation buffer's gradient
+        for l, g_ext in enumerate((g2, g4, g8, g16)):
+            (conv, _bn, group, _skip), (left, _s) = self._UP[3 - l], self._CAT[l]
+            dcat = block_back(group, l, d)
+            dskip.append(dcat[:, left:])
+            d = up_back(conv, dcat, left, l, g_ext)
+        for l in (3, 2, 1, 0):
+            conv, _bn, group = self._DOWN[l]
+            d = down_back(conv, block_back(group, l + 1, d), l, dskip[l])
         conv_back("conv0p1s1", bn_back("conv0p1s1", d), None, False, need_dx=False)   # feats never requires grad
         return grads
 

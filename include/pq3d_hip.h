@@ -1312,6 +1312,49 @@ int pq3d_allreduce_grads_wire(void* comm, float* grads, int64_t count, void* scr
  * per % 8 == 0 -- so that the W > 1 arithmetic is checked on a one-GPU box (tests/test_gpu_comm.py) */
 int pq3d_test_wire_reduce(const void* recv, void* shard, int64_t per, int32_t world, int32_t mean, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scene preparation for instance segmentation (csrc/scene_prep.hip): the per-scene host work of the reference's
+ * dataloader (data/datasets/sceneverse_instseg.py get_scene / sample_query: np.floor(coordinates / voxel_size),
+ * ME.utils.sparse_quantize, fpsample.bucket_fps_kdline_sampling) for a batch of ragged scenes.  Scene b's rows of a
+ * concatenated array are [offsets[b], offsets[b+1]); `offsets` is a HOST array of B + 1 int64 (offsets[0] = 0, every scene
+ * non-empty): the tables travel to the kernels as kernel arguments.
+ *
+ * pq3d_voxelize: coordinates [P, 3] fp32.  q = floor(x / voxel_size) with the correctly rounded fp32 division (never the
+ *   reciprocal).  Points with equal (scene, q) form a voxel; its representative is its LOWEST point index; the voxels of a
+ *   scene are numbered by ascending representative.  Outputs: unique_map [P] int64 (first V entries: representative of every
+ *   voxel, local to its scene, scene after scene), inverse_map [P] int64 (voxel of every point, local to its scene),
+ *   voxel_coordinates [P, 4] int32 (first V rows: scene, qx, qy, qz), meta [B + 2] int64 = {first voxel of scene 0 .. B - 1,
+ *   V, error bits}: bit 1 a non-finite coordinate, bit 2 a q outside [-2^19 + 8, 2^19 - 8) (the range of the packed 64-bit
+ *   key, as pq3d_sparse_nbr's callers check it).  Such points belong to no voxel (inverse_map = -1).
+ *   Workspace: keys [capacity] 8-byte words and rep [capacity] int32 (the hash table; capacity a power of two >= 2 P),
+ *   slot / pv [P] int32, bsum [ceil(P / PQ3D_VOXELIZE_BLOCK)] int32.  Nothing in the outputs depends on the order in which
+ *   threads claim table slots: two calls give the same bits.  No host synchronisation (the caller reads meta).
+ *
+ * pq3d_fps_scene: exact farthest point sampling of M of the N_b points of every scene, points [N, 3] fp32 (finite):
+ *   dist = +inf; the first sample is start_idx; per step d = (dx*dx + dy*dy) + dz*dz in fp32 without contraction,
+ *   dist = min(dist, d), next sample = arg-max of dist, ties to the SMALLEST caller index.  idx [B, M] int32, caller rows
+ *   local to the scene.  One workgroup per scene, no communication between workgroups.
+ *   pq3d_fps_scene_rows -> rows of the workspace (every scene padded to whole tiles), or -1.
+ *   pq3d_fps_scene_keys: keys [N] int64 <- (scene << 32) | Morton code of the point inside its scene's box; bbox [B, 6]
+ *   fp32 scratch.  The caller sorts the keys; perm [N] int64 = the sorting permutation (source row of every sorted
+ *   position; any permutation inside each scene gives the same idx, the order only decides how much is pruned).
+ *   pq3d_fps_scene: ws [ws_rows] 16-byte rows, cidx [ws_rows] int32, tilebox [ws_rows / 256 * 6] fp32 scratch;
+ *   scanned (nullable) [B] int64 <- tiles re-scanned over the M - 1 steps (tiles per scene: ceil(N_b / T), T = 256 when
+ *   every N_b <= 2^18, else 1024).
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_VOXELIZE_MAX_SCENES 8
+#define PQ3D_VOXELIZE_MAX_POINTS (1 << 24)
+#define PQ3D_VOXELIZE_BLOCK 2048
+#define PQ3D_FPS_MAX_SCENES 64
+#define PQ3D_FPS_MAX_POINTS (1 << 20)
+int pq3d_voxelize(const float* coordinates, const int64_t* offsets, int32_t B, float voxel_size, int64_t capacity, void* keys,
+                  int32_t* rep, int32_t* slot, int32_t* pv, int32_t* bsum, int64_t* unique_map, int64_t* inverse_map,
+                  int32_t* voxel_coordinates, int64_t* meta, void* stream);
+int64_t pq3d_fps_scene_rows(const int64_t* offsets, int32_t B);
+int pq3d_fps_scene_keys(const float* points, const int64_t* offsets, int32_t B, float* bbox, int64_t* keys, void* stream);
+int pq3d_fps_scene(const float* points, const int64_t* offsets, int32_t B, const int64_t* perm, int32_t M, int32_t start_idx,
+                   void* ws, int64_t ws_rows, int32_t* cidx, float* tilebox, int32_t* idx, int64_t* scanned, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

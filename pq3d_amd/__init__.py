@@ -13,4 +13,7 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
     if name == "Res16UNet34C":
         from .sparse import Res16UNet34C
         return Res16UNet34C
+    if name in ("voxelize", "farthest_point_sample", "prepare_instseg_batch"):
+        from . import scene
+        return getattr(scene, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

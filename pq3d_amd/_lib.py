@@ -396,9 +396,15 @@ _SIGS = {
     "pq3d_allreduce_wire_scratch_bytes": [C.c_int32, C.c_int64],
     "pq3d_allreduce_grads_wire": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "pq3d_test_wire_reduce": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
+    # scene preparation: voxelize + whole-scene farthest point sampling (csrc/scene_prep.hip); `offsets` are host arrays
+    "pq3d_voxelize": [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 10,
+    "pq3d_fps_scene_rows": [C.c_void_p, C.c_int32],
+    "pq3d_fps_scene_keys": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_fps_scene": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] +
+                      [C.c_void_p] * 5,
 }
 _RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
-          "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats"}   # size queries: bytes (or -1), not a status code
+          "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows"}   # size queries: bytes (or -1), not a status code
 EXPORTS = sorted(list(_SIGS) + ["pq3d_last_error", "pq3d_version"])
 
 

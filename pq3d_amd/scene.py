@@ -1,0 +1,203 @@
+"""Instance-segmentation scenes prepared on the GPU (csrc/scene_prep.hip): from raw points to the batch that
+``Query3DUnified`` (stage 1), ``instance_predictions`` and ``InstSegAP`` read.
+
+The reference does this on the host, one scene at a time, with MinkowskiEngine, torch_scatter and fpsample
+(data/datasets/sceneverse_instseg.py get_scene / sample_query, data/datasets/instseg_wrapper.py collate_fn):
+
+    voxel_coordinates = np.floor(coordinates / voxel_size)
+    _, unique_map, inverse_map = ME.utils.sparse_quantize(voxel_coordinates, return_index=True, return_inverse=True)
+    fps_idx = fpsample.bucket_fps_kdline_sampling(voxel_coordinates[unique_map], num_queries, h=3)
+    query_locs = coordinates[fps_idx]
+    ME.utils.sparse_collate(...), pad_sequence(...)
+
+Rules (the restatement in tests/scene_prep_ref.py is the specification):
+  voxelize   q = floor(x / fp32(voxel_size)), correctly rounded fp32 division; a voxel's representative is its lowest point
+             index, a scene's voxels are ordered by ascending representative; ``inverse_map`` is local to the scene.
+             MinkowskiEngine 0.5's own representative and order are not pinned by execution (the library is not
+             available); nothing downstream depends on them (``CoordPyramid`` re-sorts).
+  FPS        exact: dist = +inf, first sample ``start_idx``, d = (dx*dx + dy*dy) + dz*dz in fp32, dist = min(dist, d), next
+             = arg-max, ties to the smallest caller index.  fpsample's start index and tie order are not pinned either.
+One device-to-host read per ``voxelize`` (the voxel counts and the error word); ``farthest_point_sample`` has none."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import collate, ops
+
+MAX_SCENES = 8                 # PQ3D_VOXELIZE_MAX_SCENES (the packed key of sparse._pack has 3 scene bits)
+MAX_POINTS = 1 << 24           # PQ3D_VOXELIZE_MAX_POINTS
+BLOCK = 2048                   # PQ3D_VOXELIZE_BLOCK
+FPS_MAX_SCENES = 64            # PQ3D_FPS_MAX_SCENES
+FPS_MAX_POINTS = 1 << 20       # PQ3D_FPS_MAX_POINTS
+_ERRORS = {1: "coordinates hold non-finite values",
+           2: "floor(coordinates / voxel_size) leaves [-2^19 + 8, 2^19 - 8)",
+           4: "voxel hash table overflow"}
+
+
+def _scenes(ts: Sequence[torch.Tensor], what: str, max_scenes: int) -> Tuple[torch.Tensor, C.Array, List[int]]:
+    """Concatenated fp32 [N, 3] device tensor, the host offsets array and the per-scene lengths."""
+    if len(ts) < 1 or len(ts) > max_scenes:
+        raise ValueError(f"{what}: between 1 and {max_scenes} scenes, got {len(ts)}")
+    for t in ts:
+        if not t.is_cuda:
+            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1 or t.device != ts[0].device:
+            raise ValueError(f"{what}: every scene is a non-empty [N, 3] fp32 tensor on one device")
+    lens = [int(t.shape[0]) for t in ts]
+    off = (C.c_int64 * (len(ts) + 1))(0, *np.cumsum(lens).tolist())
+    return (ts[0] if len(ts) == 1 else torch.cat(list(ts), 0)).contiguous(), off, lens
+
+
+def voxelize(coordinates: Sequence[torch.Tensor], voxel_size: float):
+    """``coordinates``: per-scene [P_b, 3] fp32 device tensors (at most 8 scenes).  Returns ``voxel_coordinates`` [V, 1+3]
+    int32 (scene, qx, qy, qz; scene after scene: sparse_collate's layout), ``unique_map`` (per scene [V_b] int64: the
+    representative point of every voxel) and ``inverse_map`` (per scene [P_b] int64: the voxel of every point, local to the
+    scene: ``voxel_to_full_maps``).  Non-finite or out-of-range coordinates raise ValueError."""
+    pts, off, lens = _scenes(coordinates, "voxelize", MAX_SCENES)
+    vs = float(np.float32(voxel_size))
+    if not (np.isfinite(vs) and vs > 0.0):
+        raise ValueError(f"voxel_size must be a finite number > 0, got {voxel_size}")
+    B, P, dev = len(lens), sum(lens), pts.device
+    if P > MAX_POINTS:
+        raise ValueError(f"voxelize: at most {MAX_POINTS} points per call, got {P}")
+    cap = 1 << max(1, (2 * P - 1).bit_length())
+    keys = torch.empty(cap, dtype=torch.int64, device=dev)
+    i32 = torch.empty(cap + 2 * P + (P + BLOCK - 1) // BLOCK, dtype=torch.int32, device=dev)
+    rep, slot, pv, bsum = i32[:cap], i32[cap:cap + P], i32[cap + P:cap + 2 * P], i32[cap + 2 * P:]
+    unique_map = torch.empty(P, dtype=torch.int64, device=dev)
+    inverse_map = torch.empty(P, dtype=torch.int64, device=dev)
+    vcoord = torch.empty(P, 4, dtype=torch.int32, device=dev)
+    meta = torch.empty(B + 2, dtype=torch.int64, device=dev)
+    L.call("pq3d_voxelize", pts, C.cast(off, C.c_void_p), B, vs, cap, keys, rep, slot, pv, bsum, unique_map, inverse_map, vcoord, meta)
+    m = meta.tolist()                                             # (host sync: outside any graph)
+    if m[B + 1]:
+        raise ValueError("voxelize: " + "; ".join(t for bit, t in _ERRORS.items() if m[B + 1] & bit))
+    vofs = m[:B + 1]
+    return (vcoord[:vofs[B]], [unique_map[vofs[b]:vofs[b + 1]] for b in range(B)],
+            list(torch.split(inverse_map, lens)))
+
+
+def farthest_point_sample(points: Sequence[torch.Tensor], m: int, start_idx: int = 0, *, return_scanned: bool = False):
+    """Exact farthest point sampling of ``m`` of the points of every scene (per-scene [N_b, 3] fp32 device tensors with finite
+    values, N_b up to 2^20): [B, m] int64 rows of each scene, the first one ``start_idx``; ties go to the smallest row.
+    ``return_scanned``: also the per-scene count [B] int64 of tiles the pruning re-scanned over the m - 1 steps and the
+    number of tiles per scene (a list).  No host synchronisation."""
+    pts, off, lens = _scenes(points, "farthest_point_sample", FPS_MAX_SCENES)
+    m, start_idx = int(m), int(start_idx)
+    if m < 1 or m > min(lens):
+        raise ValueError(f"farthest_point_sample: need 1 <= m <= the smallest scene ({min(lens)} points), got m = {m}")
+    if max(lens) > FPS_MAX_POINTS:
+        raise ValueError(f"farthest_point_sample: at most {FPS_MAX_POINTS} points per scene, got {max(lens)}")
+    if not 0 <= start_idx < min(lens):
+        raise ValueError(f"farthest_point_sample: start_idx {start_idx} outside the smallest scene ({min(lens)} points)")
+    B, N, dev = len(lens), sum(lens), pts.device
+    offp = C.cast(off, C.c_void_p)
+    rows = int(L.lib().pq3d_fps_scene_rows(offp, B))
+    L.check(0 if rows >= 0 else -1, "pq3d_fps_scene_rows")
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    f32 = torch.empty(B * 6 + rows * 4 + rows // 256 * 6 + 4, dtype=torch.float32, device=dev)
+    ws_at = (B * 6 + 3) // 4 * 4                                   # 16-byte rows
+    bbox, ws, tilebox = f32[:B * 6], f32[ws_at:ws_at + rows * 4], f32[ws_at + rows * 4:]
+    L.call("pq3d_fps_scene_keys", pts, offp, B, bbox, keys)
+    perm = torch.sort(keys, stable=True).indices
+    cidx = torch.empty(rows, dtype=torch.int32, device=dev)
+    idx = torch.empty(B, m, dtype=torch.int32, device=dev)
+    scanned = torch.zeros(B, dtype=torch.int64, device=dev) if return_scanned else None
+    L.call("pq3d_fps_scene", pts, offp, B, perm, m, start_idx, ws, rows, cidx, tilebox, idx, scanned)
+    if return_scanned:
+        T = 256 if max(lens) <= 1 << 18 else 1024
+        return idx.long(), scanned, [(n + T - 1) // T for n in lens]
+    return idx.long()
+
+
+def _centers(coordinates: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], sizes: Sequence[int]) -> List[torch.Tensor]:
+    """torch_scatter.scatter_mean(coordinates[b], ids[b], dim=0) per scene with dim_size = sizes[b], as ONE segment reduction of
+    the batch (ids offset by b * max size); an id no point carries gives a zero row."""
+    S = max(sizes)
+    flat = torch.cat([i + b * S for b, i in enumerate(ids)])
+    table = ops.scatter_mean(torch.cat(list(coordinates), 0).contiguous(), flat, len(ids) * S)
+    return [table[b * S:b * S + sizes[b]] for b in range(len(ids))]
+
+
+def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequence[torch.Tensor],
+                          point2segment: Sequence[torch.Tensor], voxel_size: float, num_queries: int, *,
+                          query_sample_strategy: str = "fps", point2instance: Optional[Sequence[torch.Tensor]] = None,
+                          instance_ids: Optional[Sequence[torch.Tensor]] = None, query_from: str = "points") -> Dict[str, object]:
+    """get_scene + collate_fn of the reference for a batch of scenes, on the device.  Per scene b: ``coordinates[b]`` [P_b, 3]
+    fp32, ``features[b]`` [P_b, F] fp32 (the reference: colour | xyz, so that ``voxel_features[:, -3:]`` are coordinates),
+    ``point2segment[b]`` [P_b] int64; optional ``point2instance[b]`` [P_b] int64 (-1 = no instance) with
+    ``instance_ids[b]`` [I_b] int64 for the object centres.
+
+    Returns the keys the model and the evaluators read: ``voxel_coordinates`` [V, 4] int32 and ``voxel_features`` [V, F]
+    (``features[unique_map]``), the per-scene lists ``voxel2segment`` (``point2segment[unique_map]``), ``coordinates``
+    (``voxel_features[:, -3:]``), ``voxel_to_full_maps``, ``segment_to_full_maps``, ``raw_coordinates``, and, padded with
+    collate.pad_sequence, ``seg_center`` / ``seg_pad_masks``, ``obj_center`` / ``obj_pad_masks`` (when instances are given),
+    ``query_locs`` / ``query_pad_masks``, ``coord_min`` / ``coord_max`` [B, 3].
+
+    Centres are scatter_mean over the points: dim_size = largest id + 1, an id without points gives a zero row, instance -1
+    counts as ``instance_ids.max() + 1`` (as the reference does) and ``obj_center`` is the table at ``instance_ids``.
+
+    ``query_sample_strategy="fps"``: farthest point sampling of ``num_queries`` voxels on the float voxel lattice
+    coordinates.  ``query_from="points"`` reproduces the reference, quirk included: ``query_locs = coordinates[fps_idx]``
+    indexes the RAW POINTS with VOXEL indices (sample_query is handed the unquantised cloud), so the locations are those of
+    the first V_b points of the file, not of the sampled voxels.  ``query_from="voxels"`` gives
+    ``coordinates[unique_map[fps_idx]]``, the sampled voxels' representative points.  ``"gt"`` returns ``obj_center``.
+    Host reads: one in ``voxelize``, one for the largest segment / instance ids."""
+    B = len(coordinates)
+    if not (len(features) == len(point2segment) == B):
+        raise ValueError("one features / point2segment entry per scene")
+    if query_sample_strategy not in ("fps", "gt"):
+        raise NotImplementedError(f"{query_sample_strategy} is not implemented")
+    if query_from not in ("points", "voxels"):
+        raise ValueError(f"query_from must be 'points' or 'voxels', got {query_from!r}")
+    with_obj = point2instance is not None
+    if with_obj and (instance_ids is None or len(point2instance) != B or len(instance_ids) != B):
+        raise ValueError("point2instance needs instance_ids, one entry per scene each")
+    if query_sample_strategy == "gt" and not with_obj:
+        raise ValueError("query_sample_strategy='gt' needs point2instance and instance_ids")
+    voxel_coordinates, unique_map, inverse_map = voxelize(coordinates, voxel_size)
+    for b in range(B):
+        if features[b].shape[0] != coordinates[b].shape[0] or point2segment[b].shape != coordinates[b].shape[:1]:
+            raise ValueError(f"scene {b}: features [P, F] and point2segment [P] must match coordinates [P, 3]")
+        if point2segment[b].dtype != torch.int64 or features[b].dtype != torch.float32:
+            raise ValueError("features are fp32, point2segment int64")
+    vfeat = [features[b][unique_map[b]] for b in range(B)]
+    out: Dict[str, object] = dict(
+        voxel_coordinates=voxel_coordinates, voxel_features=torch.cat(vfeat, 0),
+        voxel2segment=[point2segment[b][unique_map[b]] for b in range(B)], coordinates=[f[:, -3:] for f in vfeat],
+        voxel_to_full_maps=inverse_map, segment_to_full_maps=list(point2segment), raw_coordinates=list(coordinates))
+    # table sizes of the scatter_means (largest id + 1): one read for the whole batch
+    tops = [point2segment[b].max() for b in range(B)]
+    if with_obj:
+        tops += [instance_ids[b].max() for b in range(B)] + [point2instance[b].max() for b in range(B)]
+    tops = torch.stack(tops).tolist()                            # (host sync)
+    seg_center = _centers(coordinates, point2segment, [t + 1 for t in tops[:B]])
+    ones = lambda ts: [torch.ones(t.shape[0], dtype=torch.bool, device=t.device) for t in ts]
+    out["seg_center"], out["seg_pad_masks"] = collate.pad_sequence(seg_center), collate.pad_sequence(ones(seg_center))
+    if with_obj:
+        p2i = [torch.where(point2instance[b] == -1, instance_ids[b].max() + 1, point2instance[b]) for b in range(B)]
+        sizes = [max(tops[2 * B + b], tops[B + b] + 1) + 1 for b in range(B)]     # (covers the row that -1 maps to)
+        table = _centers(coordinates, p2i, sizes)
+        obj_center = [table[b][instance_ids[b]] for b in range(B)]
+        out["obj_center"], out["obj_pad_masks"] = collate.pad_sequence(obj_center), collate.pad_sequence(ones(obj_center))
+    if query_sample_strategy == "fps":
+        V = [int(u.shape[0]) for u in unique_map]
+        if int(num_queries) < 1 or int(num_queries) > min(V):
+            raise ValueError(f"num_queries = {num_queries} needs 1 <= num_queries <= the voxels of the smallest scene ({min(V)})")
+        lattice = list(torch.split(voxel_coordinates[:, 1:].float(), V))
+        fps_idx = farthest_point_sample(lattice, int(num_queries))
+        if query_from == "points":
+            locs = [coordinates[b][fps_idx[b]] for b in range(B)]
+        else:
+            locs = [coordinates[b][unique_map[b][fps_idx[b]]] for b in range(B)]
+        out["query_locs"], out["query_pad_masks"] = collate.pad_sequence(locs), collate.pad_sequence(ones(locs))
+    else:
+        out["query_locs"], out["query_pad_masks"] = out["obj_center"], out["obj_pad_masks"]
+    out["coord_min"] = collate.pad_sequence([c.min(0)[0] for c in coordinates])
+    out["coord_max"] = collate.pad_sequence([c.max(0)[0] for c in coordinates])
+    return out

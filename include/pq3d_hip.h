@@ -1355,6 +1355,52 @@ int pq3d_fps_scene_keys(const float* points, const int64_t* offsets, int32_t B, 
 int pq3d_fps_scene(const float* points, const int64_t* offsets, int32_t B, const int64_t* perm, int32_t M, int32_t start_idx,
                    void* ws, int64_t ws_rows, int32_t* cidx, float* tilebox, int32_t* idx, int64_t* scanned, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Instance-segmentation training targets from per-point ids (csrc/instance_targets.hip): what the reference
+ * builds per scene on the host (data/datasets/sceneverse_instseg.py extract_inst_info: np.unique, a dense int64 full_masks,
+ * a fancy-index scatter) and pads in instseg_wrapper.collate_fn, for a batch of B <= PQ3D_INSTANCE_MAX_SCENES ragged scenes
+ * concatenated as for pq3d_voxelize (`offsets`: HOST array of B + 1 int64, offsets[0] = 0, every scene non-empty, at most
+ * PQ3D_VOXELIZE_MAX_POINTS points per call).  point2instance / point2semantic / point2segment: [P] int64 each.
+ *
+ * Rules per scene: the distinct values of point2instance in ascending order are the candidate instances; an instance's
+ * label is point2semantic at its LOWEST point index; an instance is kept iff its id is not -1 and its label is none of the
+ * n_filter values of `filter` (a HOST array, n_filter <= PQ3D_INSTANCE_MAX_FILTER); kept instances are numbered (rows) in
+ * ascending id order.  Every output is an integer or 0/1 and does not depend on the order in which threads run: atomics
+ * decide only who writes first (atomicMin of point indices, exchange of a mask cell: the thread that saw 0 bumps the row's
+ * integer count).
+ *
+ * No input value is used as an index before it is range-checked; a point with a bad value is skipped and sets a bit of
+ * err[0]:   1  point2instance < -1 or >= PQ3D_INSTANCE_MAX_IDS
+ *           2  point2segment < 0 or >= seg_limit (padded form: seg_limit = Ns)
+ *           4  more than max_rows kept instances (rows past max_rows are dropped; n_inst is clamped to max_rows)
+ *
+ * pq3d_instance_tables: first / rank [B, PQ3D_INSTANCE_MAX_IDS + 1] int32 workspace (slot id + 1 of scene b: lowest point
+ *   index, local to the scene; row of the instance or -1).  Outputs: instance_ids (nullable) and labels [B, max_rows]
+ *   int64 (labels zeroed first: 0 past n_inst; 1 <= max_rows <= PQ3D_INSTANCE_MAX_IDS), n_inst [B] int32, seg_len [B]
+ *   int32 (largest valid point2segment + 1), err [1] int32.  1 <= seg_limit <= PQ3D_INSTANCE_MAX_SEGMENTS.
+ * pq3d_instance_masks: after the caller has read n_inst and seg_len: rows / cols HOST arrays of B int64 (G_b, S_b).
+ *   segment_masks: bytes, scene after scene row-major [G_b, S_b], ZEROED BY THE CALLER; cells are set to 1.  full_masks
+ *   (nullable, with prank): bytes, scene after scene row-major [G_b, P_b], every byte written (0 / 1) with 16-byte stores;
+ *   prank: int16 workspace of sum_b roundup(P_b, 16) entries (a point's row or -1, scenes padded to 16 entries).
+ * pq3d_instance_masks_padded: the layout of losses.PaddedTargets: T [B, Nt, Ns] fp32 (zeroed here, cells set to 1),
+ *   t_sum [B, Nt] fp32 = the exact number of distinct segments of every row; cnt [B, Nt] int32 workspace.  `rank` from
+ *   pq3d_instance_tables called with max_rows = Nt and seg_limit = Ns (labels / seg_len / n_inst are PaddedTargets' own).
+ * No host synchronisation in any of the three.
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_INSTANCE_MAX_SCENES 8
+#define PQ3D_INSTANCE_MAX_IDS 4096
+#define PQ3D_INSTANCE_MAX_FILTER 16
+#define PQ3D_INSTANCE_MAX_SEGMENTS (1 << 24)
+int pq3d_instance_tables(const int64_t* point2instance, const int64_t* point2semantic, const int64_t* point2segment,
+                         const int64_t* offsets, int32_t B, const int64_t* filter, int32_t n_filter, int64_t seg_limit,
+                         int32_t max_rows, int32_t* first, int32_t* rank, int64_t* instance_ids, int64_t* labels, int32_t* n_inst,
+                         int32_t* seg_len, int32_t* err, void* stream);
+int pq3d_instance_masks(const int64_t* point2instance, const int64_t* point2segment, const int64_t* offsets, int32_t B,
+                        const int32_t* rank, const int64_t* rows, const int64_t* cols, void* segment_masks, void* prank,
+                        void* full_masks, void* stream);
+int pq3d_instance_masks_padded(const int64_t* point2instance, const int64_t* point2segment, const int64_t* offsets, int32_t B,
+                               const int32_t* rank, int32_t Ns, int32_t Nt, float* T, int32_t* cnt, float* t_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

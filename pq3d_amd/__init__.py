@@ -13,7 +13,8 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
     if name == "Res16UNet34C":
         from .sparse import Res16UNet34C
         return Res16UNet34C
-    if name in ("voxelize", "farthest_point_sample", "prepare_instseg_batch"):
+    if name in ("voxelize", "farthest_point_sample", "prepare_instseg_batch", "instance_targets", "padded_instance_targets",
+                "check_instance_targets"):
         from . import scene
         return getattr(scene, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -402,6 +402,11 @@ _SIGS = {
     "pq3d_fps_scene_keys": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "pq3d_fps_scene": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] +
                       [C.c_void_p] * 5,
+    # instance-segmentation training targets from per-point ids (csrc/instance_targets.hip); `offsets`, `filter`, `rows`, `cols` are
+    # host arrays
+    "pq3d_instance_tables": [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 8,
+    "pq3d_instance_masks": [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 7,
+    "pq3d_instance_masks_padded": [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4,
 }
 _RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
           "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows"}   # size queries: bytes (or -1), not a status code

@@ -37,6 +37,13 @@ FPS_MAX_POINTS = 1 << 20       # PQ3D_FPS_MAX_POINTS
 _ERRORS = {1: "coordinates hold non-finite values",
            2: "floor(coordinates / voxel_size) leaves [-2^19 + 8, 2^19 - 8)",
            4: "voxel hash table overflow"}
+INSTANCE_MAX_SCENES = 8        # PQ3D_INSTANCE_MAX_SCENES
+INSTANCE_MAX_IDS = 4096        # PQ3D_INSTANCE_MAX_IDS: instance ids lie in [-1, 4096)
+INSTANCE_MAX_FILTER = 16       # PQ3D_INSTANCE_MAX_FILTER
+INSTANCE_MAX_SEGMENTS = 1 << 24   # PQ3D_INSTANCE_MAX_SEGMENTS
+_INSTANCE_ERRORS = {1: f"point2instance holds values outside [-1, {INSTANCE_MAX_IDS})",
+                    2: "point2segment holds negative values or values beyond the segment limit (Ns in the padded form)",
+                    4: "a scene has more kept instances than max_instances"}
 
 
 def _scenes(ts: Sequence[torch.Tensor], what: str, max_scenes: int) -> Tuple[torch.Tensor, C.Array, List[int]]:
@@ -124,10 +131,144 @@ def _centers(coordinates: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], s
     return [table[b * S:b * S + sizes[b]] for b in range(len(ids))]
 
 
+# ------------------------------------------------------------------------------------------ training targets
+def _id_scenes(p2i, sem, seg, what: str):
+    """The three per-point id arrays of a batch, concatenated: int64 [P] device tensors, the host offsets array, the lengths."""
+    B = len(p2i)
+    if B < 1 or B > INSTANCE_MAX_SCENES or len(sem) != B or len(seg) != B:
+        raise ValueError(f"{what}: between 1 and {INSTANCE_MAX_SCENES} scenes, one point2instance / point2semantic / point2segment each")
+    for b in range(B):
+        for t in (p2i[b], sem[b], seg[b]):
+            if not t.is_cuda:
+                raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+            if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] < 1 or t.shape != p2i[b].shape or t.device != p2i[0].device:
+                raise ValueError(f"{what}: every scene has three non-empty [P_b] int64 tensors on one device")
+    lens = [int(t.shape[0]) for t in p2i]
+    if sum(lens) > MAX_POINTS:
+        raise ValueError(f"{what}: at most {MAX_POINTS} points per call, got {sum(lens)}")
+    off = (C.c_int64 * (B + 1))(0, *np.cumsum(lens).tolist())
+    cat = lambda ts: (ts[0] if B == 1 else torch.cat(list(ts))).contiguous()
+    return cat(p2i), cat(sem), cat(seg), off, lens
+
+
+def _filter(filter_out_classes) -> Tuple[C.c_void_p, int]:
+    """The host array of the filtered classes (as the pointer the entry point takes) and its length."""
+    f = [int(c) for c in filter_out_classes]
+    if len(f) > INSTANCE_MAX_FILTER:
+        raise ValueError(f"at most {INSTANCE_MAX_FILTER} filter_out_classes, got {len(f)}")
+    return C.cast((C.c_int64 * max(len(f), 1))(*f), C.c_void_p), len(f)
+
+
+def _instance_error(word: int, what: str) -> None:
+    if word:
+        raise ValueError(f"{what}: " + "; ".join(t for bit, t in _INSTANCE_ERRORS.items() if word & bit))
+
+
+class _InstanceTables:
+    """First half of ``instance_targets`` (the kernels before the host read): the id tables of a batch and ``meta`` [2 B + 1]
+    int32 = kept instances per scene, segments per scene, the error word.  ``masks(meta as a list)`` is the second half."""
+
+    def __init__(self, point2instance, point2semantic, point2segment, filter_out_classes):
+        self.p2i, sem, self.seg, self.off, self.lens = _id_scenes(point2instance, point2semantic, point2segment, "instance_targets")
+        B, dev = len(self.lens), self.p2i.device
+        flt, n_flt = _filter(filter_out_classes)
+        ws = torch.empty(2, B, INSTANCE_MAX_IDS + 1, dtype=torch.int32, device=dev)
+        self.rank = ws[1]
+        self.table = torch.empty(2, B, INSTANCE_MAX_IDS, dtype=torch.int64, device=dev)          # instance ids | labels
+        self.meta = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+        L.call("pq3d_instance_tables", self.p2i, sem, self.seg, C.cast(self.off, C.c_void_p), B, flt, n_flt, INSTANCE_MAX_SEGMENTS,
+               INSTANCE_MAX_IDS, ws[0], self.rank, self.table[0], self.table[1],
+               self.meta[:B], self.meta[B:2 * B], self.meta[2 * B:])
+
+    def last_ids(self) -> torch.Tensor:
+        """[B] int64: the largest kept instance id of every scene, -1 for a scene without instances (no host read)."""
+        n = self.meta[:len(self.lens)].long()
+        return torch.where(n > 0, self.table[0].gather(1, (n - 1).clamp(min=0)[:, None])[:, 0], -1)
+
+    def masks(self, meta: Sequence[int], with_full_masks: bool) -> Dict[str, list]:
+        B, dev = len(self.lens), self.p2i.device
+        _instance_error(meta[2 * B], "instance_targets")
+        G, S = meta[:B], meta[B:2 * B]
+        seg_masks = torch.zeros(sum(g * s for g, s in zip(G, S)), dtype=torch.uint8, device=dev)
+        full = torch.empty(sum(g * p for g, p in zip(G, self.lens)) if with_full_masks else 0, dtype=torch.uint8, device=dev)
+        prank = torch.empty(sum((p + 15) // 16 * 16 for p in self.lens), dtype=torch.int16, device=dev) if full.numel() else None
+        rows, cols = (C.c_int64 * B)(*G), (C.c_int64 * B)(*S)
+        L.call("pq3d_instance_masks", self.p2i, self.seg, C.cast(self.off, C.c_void_p), B, self.rank, C.cast(rows, C.c_void_p),
+               C.cast(cols, C.c_void_p), seg_masks if seg_masks.numel() else None, prank, full if full.numel() else None)
+        split = lambda flat, widths: [m.view(torch.bool).view(g, w) for m, g, w in
+                                      zip(torch.split(flat, [g * w for g, w in zip(G, widths)]), G, widths)]
+        return dict(instance_ids=[self.table[0, b, :G[b]] for b in range(B)], instance_labels=[self.table[1, b, :G[b]] for b in range(B)],
+                    segment_masks=split(seg_masks, S), full_masks=split(full, self.lens) if with_full_masks else None)
+
+
+def instance_targets(point2instance: Sequence[torch.Tensor], point2semantic: Sequence[torch.Tensor],
+                     point2segment: Sequence[torch.Tensor], *, filter_out_classes: Sequence[int] = (0, 2),
+                     with_full_masks: bool = True) -> Dict[str, Optional[list]]:
+    """The training targets of a batch of scenes (at most 8) from their per-point ids, on the device: what the reference's
+    extract_inst_info builds per scene on the host.  Per scene b three [P_b] int64 device tensors: ``point2instance`` (values
+    in [-1, 4096), -1 = no object, gaps allowed), ``point2semantic`` (any value) and ``point2segment`` (>= 0).
+
+    The distinct instance ids in ascending order are the candidates; an instance's label is ``point2semantic`` at its LOWEST
+    point index; it is kept iff its id is not -1 and its label is not in ``filter_out_classes``.  Returns per-scene lists:
+    ``instance_ids`` [G_b] int64, ``instance_labels`` [G_b] int64, ``segment_masks`` [G_b, S_b] bool (S_b = largest segment
+    id + 1; true iff some point carries (instance, segment)) and ``full_masks`` [G_b, P_b] bool (None when
+    ``with_full_masks`` is false).  G_b = 0 is legal.
+
+    The masks are ``torch.bool``, one byte per cell, where the reference's ``full_masks`` is an int64 tensor: every consumer
+    (``instseg_ap.gt_boxes``, the criterion's ``.float()``) only tests or converts the cells, and eight bytes per cell are
+    80 MB for 100 instances x 100k points.  One device-to-host read (the counts and the error word); ids outside their
+    range raise ValueError."""
+    t = _InstanceTables(point2instance, point2semantic, point2segment, filter_out_classes)
+    return t.masks(t.meta.tolist(), with_full_masks)                # (host sync: outside any graph)
+
+
+def padded_instance_targets(point2instance: Sequence[torch.Tensor], point2semantic: Sequence[torch.Tensor],
+                            point2segment: Sequence[torch.Tensor], Ns: int, max_instances: int, *,
+                            filter_out_classes: Sequence[int] = (0, 2), out=None):
+    """The same targets written straight into the padded layout the device criterion reads (``losses.PaddedTargets`` at
+    ``Nt = max_instances``, what ``SetCriterion.pad_targets`` builds in a host loop) with NO device-to-host read.  Returns
+    ``(targets, err)``: ``err`` is a device int32 word (``check_instance_targets(err)`` reads it and raises): bit 1 an
+    instance id outside [-1, 4096), bit 2 a segment id outside [0, Ns), bit 4 more than ``max_instances`` kept instances
+    in a scene; the offending points (rows) are skipped.  ``out``: an existing PaddedTargets of these shapes to fill (the
+    static buffers a captured step reads); everything in it is overwritten."""
+    from .losses import PaddedTargets
+    p2i, sem, seg, off, lens = _id_scenes(point2instance, point2semantic, point2segment, "padded_instance_targets")
+    B, dev, Ns, Nt = len(lens), p2i.device, int(Ns), int(max_instances)
+    if not (1 <= Ns <= INSTANCE_MAX_SEGMENTS and 1 <= Nt <= INSTANCE_MAX_IDS):
+        raise ValueError(f"padded_instance_targets: need 1 <= Ns <= {INSTANCE_MAX_SEGMENTS} and 1 <= max_instances <= {INSTANCE_MAX_IDS}")
+    flt, n_flt = _filter(filter_out_classes)
+    if out is None:
+        out = PaddedTargets(torch.empty(B, Nt, Ns, dtype=torch.float32, device=dev), torch.empty(B, Nt, dtype=torch.int64, device=dev),
+                            torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                            torch.empty(B, Nt, dtype=torch.float32, device=dev))
+    else:
+        want = dict(T=((B, Nt, Ns), torch.float32), labels=((B, Nt), torch.int64), seg_len=((B,), torch.int32),
+                    n_inst_dev=((B,), torch.int32), t_sum=((B, Nt), torch.float32))
+        for k, (shape, dt) in want.items():
+            t = getattr(out, k)
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"padded_instance_targets: out.{k} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    ws = torch.empty(2 * B * (INSTANCE_MAX_IDS + 1) + B * Nt + 1, dtype=torch.int32, device=dev)
+    n = B * (INSTANCE_MAX_IDS + 1)
+    first, rank, cnt, err = ws[:n], ws[n:2 * n], ws[2 * n:2 * n + B * Nt], ws[2 * n + B * Nt:]
+    offp = C.cast(off, C.c_void_p)
+    L.call("pq3d_instance_tables", p2i, sem, seg, offp, B, flt, n_flt, Ns, Nt, first, rank,
+           None, out.labels, out.n_inst_dev, out.seg_len, err)
+    L.call("pq3d_instance_masks_padded", p2i, seg, offp, B, rank, Ns, Nt, out.T, cnt, out.t_sum)
+    return out, err
+
+
+def check_instance_targets(err: torch.Tensor) -> None:
+    """Read the error word of ``padded_instance_targets`` (a host sync) and raise ValueError with the text of its bits."""
+    _instance_error(int(err.reshape(-1)[0]), "padded_instance_targets")
+
+
 def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequence[torch.Tensor],
                           point2segment: Sequence[torch.Tensor], voxel_size: float, num_queries: int, *,
                           query_sample_strategy: str = "fps", point2instance: Optional[Sequence[torch.Tensor]] = None,
-                          instance_ids: Optional[Sequence[torch.Tensor]] = None, query_from: str = "points") -> Dict[str, object]:
+                          instance_ids: Optional[Sequence[torch.Tensor]] = None, query_from: str = "points",
+                          point2semantic: Optional[Sequence[torch.Tensor]] = None, filter_out_classes: Sequence[int] = (0, 2),
+                          offline_mask_source: Optional[str] = None) -> Dict[str, object]:
     """get_scene + collate_fn of the reference for a batch of scenes, on the device.  Per scene b: ``coordinates[b]`` [P_b, 3]
     fp32, ``features[b]`` [P_b, F] fp32 (the reference: colour | xyz, so that ``voxel_features[:, -3:]`` are coordinates),
     ``point2segment[b]`` [P_b] int64; optional ``point2instance[b]`` [P_b] int64 (-1 = no instance) with
@@ -147,7 +288,13 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
     indexes the RAW POINTS with VOXEL indices (sample_query is handed the unquantised cloud), so the locations are those of
     the first V_b points of the file, not of the sampled voxels.  ``query_from="voxels"`` gives
     ``coordinates[unique_map[fps_idx]]``, the sampled voxels' representative points.  ``"gt"`` returns ``obj_center``.
-    Host reads: one in ``voxelize``, one for the largest segment / instance ids."""
+
+    With ``point2instance`` and ``point2semantic`` ([P_b] int64 each) and no ``instance_ids`` the training targets are
+    derived from the point ids (``instance_targets`` with ``filter_out_classes``): the list keys ``instance_ids``,
+    ``instance_labels``, ``segment_masks`` and ``full_masks`` are added, and the derived ``instance_ids`` give ``obj_center``.
+    ``offline_mask_source='gt'`` then adds collate_fn's padded keys ``offline_attn_mask`` (True as masked), ``target_labels``
+    (padded with -100), ``target_masks`` (fp32) and ``target_masks_pad_masks``; any other value is not implemented.
+    Host reads: one in ``voxelize``, one for the largest segment / instance ids (and the derived targets' counts)."""
     B = len(coordinates)
     if not (len(features) == len(point2segment) == B):
         raise ValueError("one features / point2segment entry per scene")
@@ -155,11 +302,18 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
         raise NotImplementedError(f"{query_sample_strategy} is not implemented")
     if query_from not in ("points", "voxels"):
         raise ValueError(f"query_from must be 'points' or 'voxels', got {query_from!r}")
+    if offline_mask_source not in (None, "gt"):
+        raise NotImplementedError(f"{offline_mask_source} is not implemented")
     with_obj = point2instance is not None
-    if with_obj and (instance_ids is None or len(point2instance) != B or len(instance_ids) != B):
+    derive = with_obj and instance_ids is None and point2semantic is not None     # the targets come from the point ids
+    if derive and (len(point2instance) != B or len(point2semantic) != B):
+        raise ValueError("one point2instance / point2semantic entry per scene")
+    if with_obj and not derive and (instance_ids is None or len(point2instance) != B or len(instance_ids) != B):
         raise ValueError("point2instance needs instance_ids, one entry per scene each")
     if query_sample_strategy == "gt" and not with_obj:
         raise ValueError("query_sample_strategy='gt' needs point2instance and instance_ids")
+    if offline_mask_source == "gt" and not derive:
+        raise ValueError("offline_mask_source='gt' needs point2instance and point2semantic (and no instance_ids)")
     voxel_coordinates, unique_map, inverse_map = voxelize(coordinates, voxel_size)
     for b in range(B):
         if features[b].shape[0] != coordinates[b].shape[0] or point2segment[b].shape != coordinates[b].shape[:1]:
@@ -172,15 +326,32 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
         voxel2segment=[point2segment[b][unique_map[b]] for b in range(B)], coordinates=[f[:, -3:] for f in vfeat],
         voxel_to_full_maps=inverse_map, segment_to_full_maps=list(point2segment), raw_coordinates=list(coordinates))
     # table sizes of the scatter_means (largest id + 1): one read for the whole batch
+    # (derived targets: their counts and error word ride in the same read; a scene without instances counts as largest id -1)
     tops = [point2segment[b].max() for b in range(B)]
-    if with_obj:
-        tops += [instance_ids[b].max() for b in range(B)] + [point2instance[b].max() for b in range(B)]
-    tops = torch.stack(tops).tolist()                            # (host sync)
+    if derive:
+        tables = _InstanceTables(point2instance, point2semantic, point2segment, filter_out_classes)
+        last_id = tables.last_ids()
+        tops = torch.cat([torch.stack(tops), last_id, torch.stack([point2instance[b].max() for b in range(B)]), tables.meta.long()])
+    else:
+        if with_obj:
+            tops += [instance_ids[b].max() for b in range(B)] + [point2instance[b].max() for b in range(B)]
+            last_id = tops[B:2 * B]
+        tops = torch.stack(tops)
+    tops = tops.tolist()                                         # (host sync)
+    if derive:
+        targets = tables.masks(tops[3 * B:], True)
+        instance_ids = targets["instance_ids"]
+        out.update(targets)
+        if offline_mask_source == "gt":                          # collate_fn: True as masked
+            padded, padding = collate.pad_sequence_2d(targets["segment_masks"], return_mask=True)
+            out["offline_attn_mask"], out["target_masks"] = padded.logical_not(), padded.float()
+            out["target_labels"] = collate.pad_sequence(targets["instance_labels"], pad=-100)
+            out["target_masks_pad_masks"] = padding.logical_not()
     seg_center = _centers(coordinates, point2segment, [t + 1 for t in tops[:B]])
     ones = lambda ts: [torch.ones(t.shape[0], dtype=torch.bool, device=t.device) for t in ts]
     out["seg_center"], out["seg_pad_masks"] = collate.pad_sequence(seg_center), collate.pad_sequence(ones(seg_center))
     if with_obj:
-        p2i = [torch.where(point2instance[b] == -1, instance_ids[b].max() + 1, point2instance[b]) for b in range(B)]
+        p2i = [torch.where(point2instance[b] == -1, last_id[b] + 1, point2instance[b]) for b in range(B)]
         sizes = [max(tops[2 * B + b], tops[B + b] + 1) + 1 for b in range(B)]     # (covers the row that -1 maps to)
         table = _centers(coordinates, p2i, sizes)
         obj_center = [table[b][instance_ids[b]] for b in range(B)]

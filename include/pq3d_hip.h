@@ -1401,6 +1401,58 @@ int pq3d_instance_masks(const int64_t* point2instance, const int64_t* point2segm
 int pq3d_instance_masks_padded(const int64_t* point2instance, const int64_t* point2segment, const int64_t* offsets, int32_t B,
                                const int32_t* rank, int32_t Ns, int32_t Nt, float* T, int32_t* cnt, float* t_sum, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Train-time augmentation, colour normalisation and feature rows of instance-segmentation scenes (csrc/scene_augment.hip,
+ * DESIGN 7e): what the reference's get_scene does per scene on the host with numpy, volumentations and albumentations
+ * (data/datasets/sceneverse_instseg.py), for a batch of B <= PQ3D_VOXELIZE_MAX_SCENES ragged scenes concatenated as for
+ * pq3d_voxelize (`offsets`: HOST array of B + 1 int64, offsets[0] = 0, every scene non-empty, at most
+ * PQ3D_VOXELIZE_MAX_POINTS points per call).  coordinates / colors [P, 3] fp32 in, coordinates_out [P, 3] and features_out
+ * [P, 6] fp32 (colour | xyz) out.  One parameter row (pq3d_scene_augment_params, PQ3D_SCENE_AUGMENT_K floats) per scene,
+ * drawn on the host.
+ *
+ * Every step is ONE IEEE fp32 operation in the order written (no contraction); a stage whose flag is 0 is skipped.
+ *   stats    sum_k = fp64 sum of x[:, k] (fixed order), mn_k / mx_k fp32 min / max, mean_k = fp32(sum_k / fp64(P))
+ *   centre   x1 = x - mean
+ *   offset   lo = mn - mean, hi = mx - mean, off = ((hi - lo) * u + lo) * 0.5f, x2 = x1 + off
+ *   flip     axes k = 0, 1 with flip[k] != 0: cmax = (mx - mean) + off, x3 = cmax - x2 (a stage that is off leaves its term out)
+ *   scale    x4 = x3 * scale
+ *   rotate   rot[0], rot[1], rot[2] in turn (row-major 3 x 3): y_i = (R_i0 * x_0 + R_i1 * x_1) + R_i2 * x_2
+ *   colour   c0 = trunc(c) saturated to [0, 255] (NaN -> 0); v = c0 * alpha; v = v + beta255; c1 = trunc(clip(v));
+ *            c2 = trunc(clip(c1 + shift_k)); clip(v) = v < 0 ? 0 : (v > 255 ? 255 : v)
+ *   always   f_k = (c2_k - mean255_k) * rstd255_k; features_out = (f_0, f_1, f_2, x5_0, x5_1, x5_2)
+ * err[0]:   1  a coordinate is not finite (that scene's outputs are unspecified)
+ *           2  a colour is not finite or trunc(c) lies outside [0, 255] (saturated)
+ * No store is indexed by data.
+ *
+ * pq3d_scene_augment_ws_bytes -> bytes of the partials workspace (8-byte aligned), or -1.
+ * pq3d_scene_augment_stats: zeroes err[0]; with train != 0 writes, per block of PQ3D_SCENE_AUGMENT_BLOCK points of ONE scene,
+ *   the fp64 sums and the fp32 minima / maxima of the three axes into ws (a fixed tree inside the block, no floating-point
+ *   atomics: two runs give the same bits).  With train == 0 ws may be NULL.
+ * pq3d_scene_augment_apply: params [B] rows on the device, or NULL = evaluation: only the colour conversion, the
+ *   normalisation and the feature rows (coordinates_out = coordinates bit for bit; ws is not read).  color_consts: HOST array
+ *   of 6 floats (mean255[3], rstd255[3]).  Every workgroup folds the partials of its scenes in index order.  Must follow
+ *   pq3d_scene_augment_stats on the same stream (it ORs into the err word that call zeroed).
+ * No host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_SCENE_AUGMENT_BLOCK 2048
+#define PQ3D_SCENE_AUGMENT_K 48
+typedef struct {
+  float u[3];       /* offset stage: in [0, 1) */
+  float flip[2];    /* axes 0, 1: != 0 flips */
+  float scale[3];
+  float rot[27];    /* three row-major 3 x 3 matrices, applied in turn as R x */
+  float alpha, beta255;
+  float shift[3];
+  float on_centre, on_offset, on_flip, on_scale, on_rotate, on_colour;   /* stage flags: != 0 runs the stage */
+  float reserved[2];
+} pq3d_scene_augment_params;
+int64_t pq3d_scene_augment_ws_bytes(const int64_t* offsets, int32_t B);
+int pq3d_scene_augment_stats(const float* coordinates, const int64_t* offsets, int32_t B, int32_t train, void* ws,
+                             int64_t ws_bytes, int32_t* err, void* stream);
+int pq3d_scene_augment_apply(const float* coordinates, const float* colors, const int64_t* offsets, int32_t B,
+                             const float* params, const void* ws, int64_t ws_bytes, const float* color_consts,
+                             float* coordinates_out, float* features_out, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

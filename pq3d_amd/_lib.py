@@ -222,6 +222,14 @@ class SparseWgradDesc(C.Structure):
                [(n, C.c_void_p) for n in ("x", "nbr", "dy", "dW", "occ", "ws")] + [("ws_bytes", C.c_int64)]
 
 
+class SceneAugmentParams(C.Structure):
+    """pq3d_scene_augment_params (csrc/scene_augment.hip): one fp32 parameter row per scene."""
+    _fields_ = [("u", C.c_float * 3), ("flip", C.c_float * 2), ("scale", C.c_float * 3), ("rot", C.c_float * 27),
+                ("alpha", C.c_float), ("beta255", C.c_float), ("shift", C.c_float * 3)] + \
+               [(n, C.c_float) for n in ("on_centre", "on_offset", "on_flip", "on_scale", "on_rotate", "on_colour")] + \
+               [("reserved", C.c_float * 2)]
+
+
 _lib = None
 
 _SIGS = {
@@ -407,9 +415,14 @@ _SIGS = {
     "pq3d_instance_tables": [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 8,
     "pq3d_instance_masks": [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 7,
     "pq3d_instance_masks_padded": [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4,
+    # train-time augmentation, colour normalisation and feature rows of scenes (csrc/scene_augment.hip); `offsets` and
+    # `color_consts` are host arrays
+    "pq3d_scene_augment_ws_bytes": [C.c_void_p, C.c_int32],
+    "pq3d_scene_augment_stats": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "pq3d_scene_augment_apply": [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5,
 }
 _RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
-          "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows"}   # size queries: bytes (or -1), not a status code
+          "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows", "pq3d_scene_augment_ws_bytes"}   # size queries: bytes (or -1), not a status code
 EXPORTS = sorted(list(_SIGS) + ["pq3d_last_error", "pq3d_version"])
 
 

@@ -17,10 +17,15 @@ Rules (the restatement in tests/scene_prep_ref.py is the specification):
              available); nothing downstream depends on them (``CoordPyramid`` re-sorts).
   FPS        exact: dist = +inf, first sample ``start_idx``, d = (dx*dx + dy*dy) + dz*dz in fp32, dist = min(dist, d), next
              = arg-max, ties to the smallest caller index.  fpsample's start index and tie order are not pinned either.
-One device-to-host read per ``voxelize`` (the voxel counts and the error word); ``farthest_point_sample`` has none."""
+One device-to-host read per ``voxelize`` (the voxel counts and the error word); ``farthest_point_sample`` has none.
+
+``augment_scenes`` (csrc/scene_augment.hip) is get_scene's step before all this: the train-time augmentation of the
+points and colours, the colour normalisation and ``features = colour | xyz``, by the rule restated in
+tests/scene_augment_ref.py; its random parameters are drawn on the host by ``draw_scene_augment``."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -263,12 +268,174 @@ def check_instance_targets(err: torch.Tensor) -> None:
     _instance_error(int(err.reshape(-1)[0]), "padded_instance_targets")
 
 
-def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequence[torch.Tensor],
+# ----------------------------------------------------------------------------- train-time augmentation
+# One row of ``params``: the fields of pq3d_scene_augment_params (include/pq3d_hip.h, bound as _lib.SceneAugmentParams) as
+# {name: (first float, floats)}; this is the only place the Python side spells the layout.
+AUG_FIELDS: Dict[str, Tuple[int, int]] = {n: (getattr(L.SceneAugmentParams, n).offset // 4, getattr(L.SceneAugmentParams, n).size // 4)
+                                          for n, *_ in L.SceneAugmentParams._fields_}
+AUG_K = C.sizeof(L.SceneAugmentParams) // 4     # PQ3D_SCENE_AUGMENT_K
+AUG_STAGES = ("centre", "offset", "flip", "scale", "rotate", "colour")
+COLOR_MEAN = (0.47793125906962, 0.4303257521323044, 0.3749598901421883)      # the reference's A.Normalize constants
+COLOR_STD = (0.2834475483823543, 0.27566157565723015, 0.27018971370874995)
+_AUGMENT_ERRORS = {1: "coordinates hold non-finite values",
+                   2: "colors hold non-finite values or values whose integer part leaves [0, 255] (saturated)"}
+
+
+@dataclass(frozen=True)
+class SceneAugmentConfig:
+    """Limits of the train-time augmentation; the defaults are the two augmentation files the stage-1 configs ship
+    (volumentations: Scale3d, three RotateAroundAxis3d; albumentations: RandomBrightnessContrast, RGBShift; all
+    ``always_apply``) and get_scene's own flip probability."""
+    scale_limit: Tuple[Tuple[float, float], ...] = ((-0.1, 0.1), (-0.1, 0.1), (-0.1, 0.1))     # factor = 1 + U(lo, hi) per axis
+    rotations: Tuple[Tuple[Tuple[float, float, float], Tuple[float, float]], ...] = (           # (axis, (lo, hi) radians), in turn
+        ((0.0, 0.0, 1.0), (-3.141592653589793, 3.141592653589793)),
+        ((0.0, 1.0, 0.0), (-0.13089969389957, 0.13089969389957)),
+        ((1.0, 0.0, 0.0), (-0.13089969389957, 0.13089969389957)))
+    contrast_limit: Tuple[float, float] = (-0.2, 0.2)         # alpha = 1 + U(lo, hi)
+    brightness_limit: Tuple[float, float] = (-0.2, 0.2)       # beta = U(lo, hi), times 255 (brightness_by_max)
+    rgb_shift_limit: Tuple[Tuple[float, float], ...] = ((-20.0, 20.0), (-20.0, 20.0), (-20.0, 20.0))   # r, g, b
+    flip_p: float = 0.5
+
+    @staticmethod
+    def from_files(volume_yaml: str, image_yaml: str) -> "SceneAugmentConfig":
+        """Read the two serialised ``Compose`` files: Scale3d followed by three RotateAroundAxis3d, and
+        RandomBrightnessContrast followed by RGBShift, every one ``always_apply``.  Anything else is not implemented."""
+        import yaml
+
+        def transforms(path, want):
+            with open(path) as f:
+                ts = yaml.safe_load(f)["transform"]["transforms"]
+            names = [t["__class_fullname__"].rsplit(".", 1)[-1] for t in ts]
+            for n, t in zip(names, ts):
+                if n not in want:
+                    raise NotImplementedError(f"{path}: transform {t['__class_fullname__']} is not implemented")
+                if not t.get("always_apply", False):
+                    raise NotImplementedError(f"{path}: {n} without always_apply is not implemented")
+            if names != want:
+                raise NotImplementedError(f"{path}: expected the transforms {want} in this order, got {names}")
+            return ts
+
+        pair = lambda v: (float(v[0]), float(v[1]))
+        scale, *rots = transforms(volume_yaml, ["Scale3d"] + ["RotateAroundAxis3d"] * 3)
+        bc, shift = transforms(image_yaml, ["RandomBrightnessContrast", "RGBShift"])
+        if not bc.get("brightness_by_max", True):
+            raise NotImplementedError(f"{image_yaml}: RandomBrightnessContrast without brightness_by_max is not implemented")
+        return SceneAugmentConfig(
+            scale_limit=tuple(pair(v) for v in scale["scale_limit"]),
+            rotations=tuple((tuple(float(a) for a in r["axis"]), pair(r["rotation_limit"])) for r in rots),
+            contrast_limit=pair(bc["contrast_limit"]), brightness_limit=pair(bc["brightness_limit"]),
+            rgb_shift_limit=tuple(pair(shift[k]) for k in ("r_shift_limit", "g_shift_limit", "b_shift_limit")))
+
+
+def _rotation(axis: Sequence[float], angle: float) -> np.ndarray:
+    """Rodrigues' formula in fp64: the right-handed rotation by ``angle`` about ``axis`` through the origin, applied as R x."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) * np.cos(angle) + np.sin(angle) * K + (1.0 - np.cos(angle)) * np.outer(a, a)
+
+
+def draw_scene_augment(B: int, cfg: SceneAugmentConfig, rng: np.random.Generator, *,
+                       stages: Sequence[str] = AUG_STAGES) -> torch.Tensor:
+    """The random parameters of ``B`` scenes: a CPU fp32 tensor [B, AUG_K] of pq3d_scene_augment_params rows (``AUG_FIELDS``),
+    drawn on the host from ``rng`` (no device read); the caller copies it to the device.  ``stages``: the stages whose flag
+    is set (all by default).  Everything that depends on the conventions of volumentations / albumentations (factor
+    = 1 + U, the rotation centre and sense, alpha / beta, which channel a shift belongs to) is decided HERE and nowhere else:
+    the kernels only apply the rows."""
+    unknown = sorted(set(stages) - set(AUG_STAGES))
+    if unknown:
+        raise ValueError(f"draw_scene_augment: unknown stages {unknown} (known: {AUG_STAGES})")
+    if len(cfg.rotations) != 3 or len(cfg.scale_limit) != 3 or len(cfg.rgb_shift_limit) != 3:
+        raise ValueError("draw_scene_augment: the config needs 3 scale limits, 3 rotations and 3 shift limits")
+    rows = np.zeros((int(B), AUG_K), dtype=np.float32)
+
+    def put(row, name, value):
+        at, n = AUG_FIELDS[name]
+        row[at:at + n] = np.asarray(value, dtype=np.float64).reshape(n)
+
+    for row in rows:
+        put(row, "u", rng.random(3, dtype=np.float32))           # (drawn in fp32: a rounded fp64 draw could reach 1)
+        put(row, "flip", rng.random(2) < cfg.flip_p)
+        put(row, "scale", [1.0 + rng.uniform(lo, hi) for lo, hi in cfg.scale_limit])
+        put(row, "rot", np.stack([_rotation(axis, rng.uniform(lo, hi)) for axis, (lo, hi) in cfg.rotations]))
+        put(row, "alpha", 1.0 + rng.uniform(*cfg.contrast_limit))
+        put(row, "beta255", rng.uniform(*cfg.brightness_limit) * 255.0)
+        put(row, "shift", [rng.uniform(lo, hi) for lo, hi in cfg.rgb_shift_limit])
+        for s in AUG_STAGES:
+            put(row, "on_" + s, float(s in stages))
+    return torch.from_numpy(rows)
+
+
+def color_constants(color_mean: Sequence[float] = COLOR_MEAN, color_std: Sequence[float] = COLOR_STD) -> np.ndarray:
+    """The six fp32 constants of the Normalize stage: fp32(mean * 255) and the fp32 reciprocal of fp32(std * 255)."""
+    mean = np.asarray(color_mean, dtype=np.float64).reshape(3)
+    std = np.asarray(color_std, dtype=np.float64).reshape(3)
+    return np.concatenate([(mean * 255.0).astype(np.float32), np.float32(1.0) / (std * 255.0).astype(np.float32)])
+
+
+def augment_scenes(coordinates: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], params: Optional[torch.Tensor], *,
+                   train: bool = True, color_mean: Sequence[float] = COLOR_MEAN, color_std: Sequence[float] = COLOR_STD,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """get_scene's point-wise part for a batch of scenes (at most 8), on the device: per scene ``coordinates[b]`` [P_b, 3] and
+    ``colors[b]`` [P_b, 3] fp32 (raw colours in [0, 256)), ``params`` [B, AUG_K] fp32 device rows from ``draw_scene_augment``.
+    ``train=True``: centre, random offset, axis flips, scale, three rotations, brightness / contrast and RGB shift, each
+    under its flag; always: colour -> integer -> Normalize, ``features = colour | xyz``.  ``train=False`` (``params`` may be
+    None): the coordinates come back bit for bit.  Returns ``(coordinates_out, features_out, err)``: per-scene views of one
+    [P, 3] and one [P, 6] tensor and the device error word [1] int32 (``check_scene_augment(err)`` reads it).  Two launches,
+    no device-to-host read; the same inputs give the same bits.  ``out=(xyz [P, 3], features [P, 6])``: contiguous fp32
+    buffers to write into (the static buffers of a captured step)."""
+    pts, off, lens = _scenes(coordinates, "augment_scenes", MAX_SCENES)
+    col, _off, clens = _scenes(colors, "augment_scenes", MAX_SCENES)
+    if clens != lens or col.device != pts.device:
+        raise ValueError("augment_scenes: one [P_b, 3] colors tensor per scene, matching coordinates")
+    B, P, dev = len(lens), sum(lens), pts.device
+    if P > MAX_POINTS:
+        raise ValueError(f"augment_scenes: at most {MAX_POINTS} points per call, got {P}")
+    if train:
+        if params is None:
+            raise ValueError("augment_scenes: train=True needs params (draw_scene_augment)")
+        if not params.is_cuda:
+            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+        if params.dtype != torch.float32 or tuple(params.shape) != (B, AUG_K) or not params.is_contiguous() or params.device != dev:
+            raise ValueError(f"augment_scenes: params must be a contiguous fp32 [{B}, {AUG_K}] tensor on {dev}")
+    if out is None:
+        xyz_out, feat_out = torch.empty(P, 3, dtype=torch.float32, device=dev), torch.empty(P, 6, dtype=torch.float32, device=dev)
+    else:
+        xyz_out, feat_out = out
+        for t, w in ((xyz_out, 3), (feat_out, 6)):
+            if not t.is_cuda:
+                raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+            if t.dtype != torch.float32 or tuple(t.shape) != (P, w) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"augment_scenes: out must be contiguous fp32 tensors [{P}, 3] and [{P}, 6] on {dev}")
+    offp = C.cast(off, C.c_void_p)
+    ws_bytes = int(L.lib().pq3d_scene_augment_ws_bytes(offp, B))
+    L.check(0 if ws_bytes >= 0 else -1, "pq3d_scene_augment_ws_bytes")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if train else None
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    consts = (C.c_float * 6)(*color_constants(color_mean, color_std).tolist())
+    L.call("pq3d_scene_augment_stats", pts, offp, B, int(bool(train)), ws, ws_bytes, err)
+    L.call("pq3d_scene_augment_apply", pts, col, offp, B, params if train else None, ws, ws_bytes, C.cast(consts, C.c_void_p),
+           xyz_out, feat_out, err)
+    return list(torch.split(xyz_out, lens)), list(torch.split(feat_out, lens)), err
+
+
+def _augment_error(word: int, what: str) -> None:
+    if word:
+        raise ValueError(f"{what}: " + "; ".join(t for bit, t in _AUGMENT_ERRORS.items() if word & bit))
+
+
+def check_scene_augment(err: torch.Tensor) -> None:
+    """Read the error word of ``augment_scenes`` (a host sync) and raise ValueError with the text of its bits."""
+    _augment_error(int(err.reshape(-1)[0]), "augment_scenes")
+
+
+def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Optional[Sequence[torch.Tensor]],
                           point2segment: Sequence[torch.Tensor], voxel_size: float, num_queries: int, *,
                           query_sample_strategy: str = "fps", point2instance: Optional[Sequence[torch.Tensor]] = None,
                           instance_ids: Optional[Sequence[torch.Tensor]] = None, query_from: str = "points",
                           point2semantic: Optional[Sequence[torch.Tensor]] = None, filter_out_classes: Sequence[int] = (0, 2),
-                          offline_mask_source: Optional[str] = None) -> Dict[str, object]:
+                          offline_mask_source: Optional[str] = None, colors: Optional[Sequence[torch.Tensor]] = None,
+                          augment: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """get_scene + collate_fn of the reference for a batch of scenes, on the device.  Per scene b: ``coordinates[b]`` [P_b, 3]
     fp32, ``features[b]`` [P_b, F] fp32 (the reference: colour | xyz, so that ``voxel_features[:, -3:]`` are coordinates),
     ``point2segment[b]`` [P_b] int64; optional ``point2instance[b]`` [P_b] int64 (-1 = no instance) with
@@ -294,9 +461,21 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
     ``instance_labels``, ``segment_masks`` and ``full_masks`` are added, and the derived ``instance_ids`` give ``obj_center``.
     ``offline_mask_source='gt'`` then adds collate_fn's padded keys ``offline_attn_mask`` (True as masked), ``target_labels``
     (padded with -100), ``target_masks`` (fp32) and ``target_masks_pad_masks``; any other value is not implemented.
-    Host reads: one in ``voxelize``, one for the largest segment / instance ids (and the derived targets' counts)."""
+    Host reads: one in ``voxelize``, one for the largest segment / instance ids (and the derived targets' counts).
+
+    ``colors`` (per scene [P_b, 3] fp32 raw colours, ``features`` then None): the batch is built from
+    ``augment_scenes(coordinates, colors, augment, train=augment is not None)``: ``augment`` [B, AUG_K] device rows of
+    ``draw_scene_augment`` give the train-time augmentation, None the evaluation path (colour normalisation and the
+    feature rows only).  ``raw_coordinates`` are then the augmented coordinates, as in get_scene; the error word of
+    ``augment_scenes`` rides in the second host read."""
     B = len(coordinates)
-    if not (len(features) == len(point2segment) == B):
+    if colors is not None and features is not None:
+        raise ValueError("pass features or colors, not both")
+    if colors is None and augment is not None:
+        raise ValueError("augment needs colors")
+    if colors is None and features is None:
+        raise ValueError("one of features and colors is needed")
+    if not (len(features if colors is None else colors) == len(point2segment) == B):
         raise ValueError("one features / point2segment entry per scene")
     if query_sample_strategy not in ("fps", "gt"):
         raise NotImplementedError(f"{query_sample_strategy} is not implemented")
@@ -314,6 +493,9 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
         raise ValueError("query_sample_strategy='gt' needs point2instance and instance_ids")
     if offline_mask_source == "gt" and not derive:
         raise ValueError("offline_mask_source='gt' needs point2instance and point2semantic (and no instance_ids)")
+    aug_err = None
+    if colors is not None:
+        coordinates, features, aug_err = augment_scenes(coordinates, colors, augment, train=augment is not None)
     voxel_coordinates, unique_map, inverse_map = voxelize(coordinates, voxel_size)
     for b in range(B):
         if features[b].shape[0] != coordinates[b].shape[0] or point2segment[b].shape != coordinates[b].shape[:1]:
@@ -337,7 +519,11 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Sequenc
             tops += [instance_ids[b].max() for b in range(B)] + [point2instance[b].max() for b in range(B)]
             last_id = tops[B:2 * B]
         tops = torch.stack(tops)
+    if aug_err is not None:                                      # (the augmentation's error word rides in the same read)
+        tops = torch.cat([tops, aug_err.long()])
     tops = tops.tolist()                                         # (host sync)
+    if aug_err is not None:
+        _augment_error(tops.pop(), "prepare_instseg_batch")
     if derive:
         targets = tables.masks(tops[3 * B:], True)
         instance_ids = targets["instance_ids"]

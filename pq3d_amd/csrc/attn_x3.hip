@@ -11,10 +11,23 @@
 //   * S = K_lo q_hi + K_hi q_lo + K_hi q_hi and O += V_lo P_hi + V_hi P_lo + V_hi P_hi (small terms first): 3 MFMAs per product,
 //     ~2^-17 relative per term; O leaves in fp32 (+ a bf16 copy for the backward's delta / weight gradient).
 // Structure = attn_resident.hip's all-keys-resident forward: 8 compute waves (16 queries each) + 4 loader waves, the key/value
-// slice parked in LDS behind one barrier, online softmax per wave without further synchronisation.  Two planes double the LDS per
-// key (289 B), so a workgroup holds 512 keys at a time: the compute waves fetch and park the first 512, the loader waves hold
-// the second 512 in registers meanwhile and park them over the first half once it is consumed (<= 1024 keys per key split as
-// before: config 2 needs no split / combine launch).
+// slice parked in LDS, online softmax per wave.  Two planes double the LDS per key (289 B), so a workgroup holds 512 keys at a
+// time (stage 1, then stage 2 over it; <= 1024 keys per key split as before: config 2 needs no split / combine launch).
+// STAGING (profiles/NOTES_attn_x3_staging.md): a stage arrives in NP = 4 PIECES (128 keys; d_h = 64: 64), each behind a workgroup
+// barrier of its own, so block 0 starts once a quarter of stage 1 is parked instead of all of it:
+//   * the compute waves request piece 0 (one chunk of each plane per thread) as the first thing that goes to memory -- q rows,
+//     key-padding bytes and mask words queue behind it -- park it, (A0), and run its blocks; then (Ap), blocks of piece p, ...
+//   * the loader waves request pieces 1 .. 3 in the order of their use, pass (A0), and per piece: park it, request the next part
+//     of stage 2 into the registers it has left (a quarter behind pieces 1 and 2 each, half behind piece 3: never more than the
+//     128 registers stage 2 needs anyway), (Ap).  Once (A3) is passed pieces 0 .. 2 are consumed: three quarters of stage 2 are
+//     parked over them while piece 3 is read; the last quarter and the mask words after (B), then (C).
+//   * every wave of the workgroup executes the same barriers on every path (the count depends on the slice's block count alone,
+//     which is uniform); a block that returns early returns from block() only.
+// Loads use a uniform base per plane + a 32-bit byte offset (a scene's key/value rows span < 4 GB: checked by the launcher): with
+// 64-bit per-lane addresses the up to 32 requests a loader thread keeps in flight did not fit 168 registers.
+// Measured at config 2 (MI355X, same box, alternating runs): entry -> first barrier 6.5-7.0 us -> 3.0-3.4 us in workgroup 0, the
+// launch 33.4 / 33.5 us -> 28.0 / 28.1 us.  Arithmetic, block order, grid and key splits are untouched: outputs are bit for bit
+// what they were (tests/test_gpu_x3_staging.py).
 // d_h = 64 (the head width of the reference's shipped decoders: hidden 768, 12 heads, configs/instseg_sceneverse.yaml:95,141) runs the
 // same kernel with 256 keys per stage (both planes padded to 144-byte rows), two k steps per score tile and the K / V fragments
 // fetched per tile instead of per block (168 registers per wave): shipped stage-1 / stage-2 decoder steps 14.7 / 15.4 ms in
@@ -22,6 +35,7 @@
 // New against the bf16 kernel: a 3-D self-mask as BIT WORDS (pq3d_mask_pack: row_open folded in) staged per 512-key stage, and up
 // to 256 queries as two query halves in grid.x -- config 4's shape (200 queries, 4096 keys, self-mask) stays on this kernel.
 #include <atomic>
+#include <type_traits>
 
 #include "attn_common.h"
 
@@ -36,8 +50,14 @@ template <int DH> struct X3 {
   static constexpr int XK = 16384 / DH;              // 512 / 256
   static constexpr int XNB = XK / KB;                // 8 / 4
   static constexpr int CPR = DH / 8;                 // 16-byte chunks per key row and plane
-  static constexpr int XCH1 = XK * CPR / (XW * 64);  // chunks of one plane per compute thread, stage 1 (4)
+  static constexpr int NP = 4;                       // stage 1 arrives in NP pieces of PB 64-key blocks (128 / 64 keys)
+  static constexpr int PB = XNB / NP;                // 2 / 1
+  static constexpr int PCH = XK * CPR / NP;          // chunks of one plane per piece (512): one per compute thread (piece 0)
+  static constexpr int LCP = PCH / (XLW * 64);       // ... per loader thread and piece (pieces 1 .. NP - 1) (2)
   static constexpr int XCH2 = XK * CPR / (XLW * 64); // ... per loader thread, stage 2 (8)
+  // first stage-2 chunk a loader thread requests once piece p is parked: XCH2 / NP behind each piece but the last, the rest there
+  static constexpr int s2lo(int p) { return p >= NP ? XCH2 : (p - 1) * XCH2 / NP; }
+  static_assert(PCH == XW * 64 && LCP * XLW * 64 == PCH && PB * NP == XNB && XCH2 % NP == 0, "piece layout");
   static constexpr int MWR = 2 * XNB;                // mask words per query row and stage
   static constexpr int XMW = MWR + 1;                // + 1: conflict-free column reads
   static constexpr int MW1 = MWR * 128 / (XW * 64);  // mask words per compute thread (stage 1) / loader thread (stage 2)
@@ -46,6 +66,15 @@ template <int DH> struct X3 {
   static constexpr int LDV = AT<bf16_t, DH>::LDR;
   static constexpr int KSD = DH / 32;                // k steps of a product over d_h
 };
+
+// probe builds only (-DPQ3D_X3_TIMELINE, tools/probes/x3_timeline.py): thread 0 of workgroup (0, 0, 0) stamps wall_clock64() into
+// d.ws (unused without a key split): 0 entry, 1 first stage-1 requests issued, 2 first barrier passed, 3 last block of stage 1
+// done, 4 barrier (C) passed, 5 last block done, 6 exit
+#ifdef PQ3D_X3_TIMELINE
+#define X3_TL(i) do { if (d.ws && KS == 1 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) ((long long*)d.ws)[i] = wall_clock64(); } while (0)
+#else
+#define X3_TL(i) do { } while (0)
+#endif
 
 PQ_DEV void x3_split(const float* v, u32x4& hi, u32x4& lo) {
   hi = pack_frag<bf16_t>(v);
@@ -63,8 +92,8 @@ __global__ __launch_bounds__((XW + XLW) * 64) void attn_fwd_x3_kernel(const pq3d
   ATTN_KARG_PIN(d);
   typedef AT<bf16_t, DH> A;
   typedef X3<DH> X;
-  constexpr int LDK = X::LDK, LDV = X::LDV, XK = X::XK, XNB = X::XNB, CPR = X::CPR, XCH1 = X::XCH1, XCH2 = X::XCH2, XMW = X::XMW,
-                MWR = X::MWR, KSD = X::KSD;
+  constexpr int LDK = X::LDK, LDV = X::LDV, XK = X::XK, XNB = X::XNB, CPR = X::CPR, XCH2 = X::XCH2, XMW = X::XMW,
+                MWR = X::MWR, KSD = X::KSD, NP = X::NP, PB = X::PB, PCH = X::PCH, LCP = X::LCP;
   extern __shared__ __attribute__((aligned(16))) unsigned char xsm[];
   bf16_t* const Kh = (bf16_t*)xsm;
   bf16_t* const Kl = Kh + XK * LDK;
@@ -85,67 +114,114 @@ __global__ __launch_bounds__((XW + XLW) * 64) void attn_fwd_x3_kernel(const pq3d
   const bool wave_active = !loader && q0 < q_end, qvalid = !loader && myq < q_end;
   const int bm = d.mask_bmod > 0 ? b % d.mask_bmod : b;
   const int nwords = (d.Lk + 31) / 32;
+  X3_TL(0);
 
   // one 16-byte chunk of a key row in all four planes: global -> registers (rows past the slice / past Lk: clamped duplicates,
   // never parked / masked through kpm_s)
-  auto gload = [&](int stage, int c, u32x4& kh, u32x4& kl, u32x4& vh, u32x4& vl) {
-    const int gk = min(key_lo + stage * XK + c / CPR, d.Lk - 1), part = (c % CPR) * 8;
-    const long ko = koff + (long)gk * d.k_sl + part, vo = voff + (long)gk * d.v_sl + part;
-    kh = *(const u32x4*)((const bf16_t*)d.k + ko);
-    kl = *(const u32x4*)((const bf16_t*)d.k_lo + ko);
-    vh = *(const u32x4*)((const bf16_t*)d.v + vo);
-    vl = *(const u32x4*)((const bf16_t*)d.v_lo + vo);
+  // Addresses = a workgroup-uniform base per plane + a 32-bit byte offset (one register per K / V pair; the launcher checks that a
+  // (scene, head)'s rows span < 4 GB): the staging below keeps up to 32 requests of a thread in flight.
+  const char* const kbh = (const char*)((const bf16_t*)d.k + koff), * const kbl = (const char*)((const bf16_t*)d.k_lo + koff);
+  const char* const vbh = (const char*)((const bf16_t*)d.v + voff), * const vbl = (const char*)((const bf16_t*)d.v_lo + voff);
+  const uint32_t k_sl2 = (uint32_t)d.k_sl * 2u, v_sl2 = (uint32_t)d.v_sl * 2u;
+  // Chunk c = c0 + t with c0 a constant multiple of CPR and t the thread's index among its role's threads: row c0 / CPR + t / CPR,
+  // part t % CPR -- the thread's two terms are computed once, every chunk differs by a constant.
+  auto gload = [&](int stage, int c0, int t, u32x4& kh, u32x4& kl, u32x4& vh, u32x4& vl) {
+    const uint32_t gk = (uint32_t)min(key_lo + stage * XK + c0 / CPR + t / CPR, d.Lk - 1), part = (uint32_t)(t % CPR) * 16u;
+    const uint32_t ko = gk * k_sl2 + part, vo = gk * v_sl2 + part;
+    kh = *(const u32x4*)(kbh + ko);
+    kl = *(const u32x4*)(kbl + ko);
+    vh = *(const u32x4*)(vbh + vo);
+    vl = *(const u32x4*)(vbl + vo);
   };
-  auto park = [&](int c, const u32x4& kh, const u32x4& kl, const u32x4& vh, const u32x4& vl) {
-    *(u32x4*)&Kh[(c / CPR) * LDK + (c % CPR) * 8] = kh;
-    *(u32x4*)&Kl[(c / CPR) * LDK + (c % CPR) * 8] = kl;
-    *(u32x4*)&Vh[(c / CPR) * LDV + (c % CPR) * 8] = vh;
-    *(u32x4*)&Vl[(c / CPR) * LDV + (c % CPR) * 8] = vl;
+  auto park = [&](int c0, int t, const u32x4& kh, const u32x4& kl, const u32x4& vh, const u32x4& vl) {
+    const int ko = (t / CPR) * LDK + (t % CPR) * 8, vo = (t / CPR) * LDV + (t % CPR) * 8;
+    *(u32x4*)&Kh[ko + (c0 / CPR) * LDK] = kh;
+    *(u32x4*)&Kl[ko + (c0 / CPR) * LDK] = kl;
+    *(u32x4*)&Vh[vo + (c0 / CPR) * LDV] = vh;
+    *(u32x4*)&Vl[vo + (c0 / CPR) * LDV] = vl;
   };
   // the stage's mask words of the workgroup's 128 query rows: word (q, w) = bits[bm, q_base + q, 2 (kb_lo + 8 stage) + w]
+  const char* const mrow = MASKB ? (const char*)(d.mask_bits + (long)bm * d.Lq * nwords) : nullptr;   // uniform; <= 256 rows of nwords
   auto mask_words = [&](int stage, int t, int nthreads, uint32_t (&mw)[X::MW2], int n) {
 #pragma unroll
     for (int i = 0; i < n; ++i) {
-      const int c = t + i * nthreads, q = c / MWR, w = c % MWR;
+      const int q = t / MWR + i * (nthreads / MWR), w = t % MWR;   // word t + i nthreads (nthreads: a multiple of MWR)
       const int gq = min(q_base + q, d.Lq - 1), gw = 2 * (kb_lo + XNB * stage) + w;
-      mw[i] = gw < nwords ? d.mask_bits[((long)bm * d.Lq + gq) * nwords + gw] : 0u;
+      // clamped, not branched around (one basic block); uniform base + 32-bit byte offset as in gload
+      const uint32_t wv = *(const uint32_t*)(mrow + (uint32_t)(gq * nwords + min(gw, nwords - 1)) * 4u);
+      mw[i] = gw < nwords ? wv : 0u;
     }
   };
   auto mask_park = [&](int t, int nthreads, const uint32_t (&mw)[X::MW2], int n) {
 #pragma unroll
     for (int i = 0; i < n; ++i) {
-      const int c = t + i * nthreads;
-      msk_s[(c / MWR) * XMW + (c % MWR)] = mw[i];
+      msk_s[(t / MWR) * XMW + (t % MWR) + i * (nthreads / MWR) * XMW] = mw[i];
     }
   };
 
   // ---- loader waves: a code path of their own behind a SCALAR branch (`wave` is read through readfirstlane), so that the 128
   // registers that hold the second half of the slice are not live across the compute waves' code; same barrier sequence
   if (loader) {
-    u32x4 kh2[XCH2], kl2[XCH2], vh2[XCH2], vl2[XCH2];
-    uint32_t mw2[X::MW2];
     const int t2 = tid - XW * 64;
-    if (nb > XNB) {
+    // two straight-line bodies behind one uniform branch (with / without a second stage): no register is carried through a join
+    auto body = [&](auto with2) __attribute__((always_inline)) {
+      constexpr bool W2 = decltype(with2)::value;   // W2: nb > XNB, every piece of stage 1 exists
+      u32x4 kh1[NP - 1][LCP], kl1[NP - 1][LCP], vh1[NP - 1][LCP], vl1[NP - 1][LCP];
+      u32x4 kh2[XCH2], kl2[XCH2], vh2[XCH2], vl2[XCH2];
+      uint32_t mw2[X::MW2];
+      // pieces 1 .. NP - 1 of stage 1, requested in the order of their use before anything else of this wave goes to memory
 #pragma unroll
-      for (int i = 0; i < XCH2; ++i) gload(1, t2 + i * XLW * 64, kh2[i], kl2[i], vh2[i], vl2[i]);
-      if constexpr (MASKB) mask_words(1, t2, XLW * 64, mw2, X::MW2);
-    }
-    __syncthreads();   // (A) stage 1 parked
-    if (nb > XNB) {
-      __syncthreads();   // (B) every wave is done reading stage 1
+      for (int p = 1; p < NP; ++p)
+        if (W2 || p * PB < nb) {
 #pragma unroll
-      for (int i = 0; i < XCH2; ++i) {
-        const int c = t2 + i * XLW * 64;
-        if (c < (nk - XK) * CPR) park(c, kh2[i], kl2[i], vh2[i], vl2[i]);
+          for (int j = 0; j < LCP; ++j) gload(0, p * PCH + j * XLW * 64, t2, kh1[p - 1][j], kl1[p - 1][j], vh1[p - 1][j], vl1[p - 1][j]);
+          __builtin_amdgcn_sched_barrier(0);   // requests return in the order they are issued: keep it the order of use
+        }
+      __syncthreads();   // (A0) piece 0 parked (by the compute waves)
+#pragma unroll
+      for (int p = 1; p < NP; ++p)
+        if (W2 || p * PB < nb) {   // uniform over the workgroup
+#pragma unroll
+          for (int j = 0; j < LCP; ++j) park(p * PCH + j * XLW * 64, t2, kh1[p - 1][j], kl1[p - 1][j], vh1[p - 1][j], vl1[p - 1][j]);
+          if constexpr (W2) {
+            // stage 2 into the registers the piece has left: a quarter behind each piece but the last, the rest behind that one
+            // (the scheduler must not lift these requests over the parks: both register sets would be live at once)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = X::s2lo(p); i < X::s2lo(p + 1); ++i) gload(1, i * XLW * 64, t2, kh2[i], kl2[i], vh2[i], vl2[i]);
+            if constexpr (MASKB)
+              if (p == 1) mask_words(1, t2, XLW * 64, mw2, X::MW2);   // while the fewest registers are live
+          }
+          __syncthreads();   // (Ap) piece p parked
+        }
+      if constexpr (W2) {
+        // every wave has passed (A NP-1): pieces 0 .. NP - 2 of stage 1 are consumed, their part of stage 2 is parked over them
+        // while the last piece is still being read; the rest, and the mask words, after (B)
+        constexpr int S2A = (NP - 1) * XCH2 / NP;
+        auto park2 = [&](int i) {
+          if (i * XLW * 64 / CPR + t2 / CPR < nk - XK) park(i * XLW * 64, t2, kh2[i], kl2[i], vh2[i], vl2[i]);   // rows of the slice only
+        };
+#pragma unroll
+        for (int i = 0; i < S2A; ++i) park2(i);
+        __syncthreads();   // (B) every wave is done reading stage 1
+#pragma unroll
+        for (int i = S2A; i < XCH2; ++i) park2(i);
+        if constexpr (MASKB) mask_park(t2, XLW * 64, mw2, X::MW2);
+        __syncthreads();   // (C) stage 2 parked
       }
-      if constexpr (MASKB) mask_park(t2, XLW * 64, mw2, X::MW2);
-      __syncthreads();   // (C) stage 2 parked
-    }
+    };
+    if (nb > XNB) body(std::true_type{});
+    else body(std::false_type{});
     return;
   }
-  // ---- compute waves
+  // ---- compute waves: piece 0 (one chunk of each plane per thread) is requested first -- the q rows, the key-padding bytes and
+  // the mask words queue behind it, not in front
   u32x4 qfh[KSD], qfl[KSD];
   {
+    u32x4 kh0, kl0, vh0, vl0;
+    gload(0, 0, tid, kh0, kl0, vh0, vl0);
+    __builtin_amdgcn_sched_barrier(0);   // nothing is lifted in front of these four requests
+    X3_TL(1);
 #pragma unroll
     for (int ks = 0; ks < KSD; ++ks) {   // q row (fp32) -> hi / lo fragments: lane (i, g) holds k = 32 ks + 8 g .. + 7 of query i
       const long qo = (long)b * d.q_sb + (long)min(myq, d.Lq - 1) * d.q_sl + (long)h * d.q_sh + 32 * ks + 8 * lg;
@@ -162,14 +238,10 @@ __global__ __launch_bounds__((XW + XLW) * 64) void attn_fwd_x3_kernel(const pq3d
     }
     uint32_t mw[X::MW2];
     if constexpr (MASKB) mask_words(0, tid, XW * 64, mw, X::MW1);
-    u32x4 kh[XCH1], kl[XCH1], vh[XCH1], vl[XCH1];
-#pragma unroll
-    for (int i = 0; i < XCH1; ++i) gload(0, tid + i * XW * 64, kh[i], kl[i], vh[i], vl[i]);
 #pragma unroll
     for (int i = 0; i < 2 * XK / (XW * 64); ++i) kpm_s[tid + i * XW * 64] = kp[i];
     if constexpr (MASKB) mask_park(tid, XW * 64, mw, X::MW1);
-#pragma unroll
-    for (int i = 0; i < XCH1; ++i) park(tid + i * XW * 64, kh[i], kl[i], vh[i], vl[i]);
+    park(0, tid, kh0, kl0, vh0, vl0);
   }
 
   // online softmax in the base-2 domain (attn_resident.hip): x2 = s * (scale * log2 e), p = 2^(x2 - m2)
@@ -325,15 +397,22 @@ __global__ __launch_bounds__((XW + XLW) * 64) void attn_fwd_x3_kernel(const pq3d
       }
     }
   };
-  __syncthreads();   // (A) stage 1 parked
-  if (wave_active)
-    for (int t = 0; t < min(nb, XNB); ++t) block(t, t);
+#pragma unroll 1
+  for (int p = 0; p < NP && (p == 0 || p * PB < nb); ++p) {   // uniform over the workgroup; (A0) always, as in the loader waves
+    __syncthreads();   // (Ap) piece p parked
+    if (p == 0) X3_TL(2);
+    if (wave_active)
+      for (int t = p * PB; t < min(nb, (p + 1) * PB); ++t) block(t, t);
+  }
+  X3_TL(3);
   if (nb > XNB) {   // uniform over the workgroup
     __syncthreads();   // (B)
     __syncthreads();   // (C) the loader waves have parked stage 2 over stage 1
+    X3_TL(4);
     if (wave_active)
       for (int t = XNB; t < nb; ++t) block(t - XNB, t);
   }
+  X3_TL(5);
   l = group_sum(l);
   if (!qvalid) return;
   constexpr float LN2 = 0.693147180559945309f;
@@ -358,6 +437,7 @@ __global__ __launch_bounds__((XW + XLW) * 64) void attn_fwd_x3_kernel(const pq3d
       d.ws[(long)KS * rows * (DH + 1) + ridx] = l;
     }
   }
+  X3_TL(6);
 }
 
 template <int DH, bool DROP, bool MASKB> int launch_x3(const pq3d_attn_desc& d, hipStream_t s, int KS, int nqh, int per) {
@@ -382,6 +462,8 @@ int pq3d_attn_fwd_x3(const pq3d_attn_desc& d, hipStream_t s) {
   PQ_CHECK_ARG(!(d.mask && d.kpm), "pq3d_attn_fwd (split-bf16 planes): key padding and a 3-D mask are exclusive");
   PQ_CHECK_ARG(!((d.q_sl | d.q_sb | d.q_sh | d.o_sl | d.o_sb | d.o_sh) & 3) && !((d.k_sl | d.k_sb | d.k_sh | d.v_sl | d.v_sb | d.v_sh) & 7),
                "pq3d_attn_fwd (split-bf16 planes): strides must be multiples of 16 bytes");
+  PQ_CHECK_ARG((long)d.Lk * d.k_sl < (1L << 31) - 64 && (long)d.Lk * d.v_sl < (1L << 31) - 64 && d.k_sl >= 0 && d.v_sl >= 0,
+               "pq3d_attn_fwd (split-bf16 planes): the key / value rows of a scene must span less than 4 GB");
   PQ_CHECK_ARG(((((uintptr_t)d.k_lo) | ((uintptr_t)d.v_lo) | ((uintptr_t)d.q_bf) | ((uintptr_t)d.o_bf)) & 15) == 0,
                "pq3d_attn_fwd (split-bf16 planes): planes must be 16-byte aligned");
   const int KS = d.ksplit > 1 ? d.ksplit : 1, nkb = (d.Lk + KB - 1) / KB;

@@ -13,6 +13,7 @@
 // anything; every table bound a kernel uses comes from the host (kernel arguments), never from the data.
 #include "common.h"
 #include "instance_targets_check.h"
+#include "ragged.h"
 
 #include <limits.h>
 
@@ -23,10 +24,7 @@ constexpr int IT_NT = 1024, IT_PER = (IT_SLOTS + IT_NT - 1) / IT_NT;      // it_
 constexpr int FM_PTS = 16, FM_ROWS = 8;                                   // it_full_kernel: points per thread, mask rows per block
 static_assert(IT_CAP <= 32767, "prank holds a point's row as int16");
 
-struct ItScenes {
-  int B;
-  long long off[PQ3D_INSTANCE_MAX_SCENES + 1];
-};
+typedef SceneTable<PQ3D_INSTANCE_MAX_SCENES> ItScenes;
 
 struct ItFilter {
   int n;
@@ -40,13 +38,6 @@ struct ItMasks {
       foff[PQ3D_INSTANCE_MAX_SCENES], poff[PQ3D_INSTANCE_MAX_SCENES];
   int blk0[PQ3D_INSTANCE_MAX_SCENES + 1];
 };
-
-PQ_DEV int it_scene(const ItScenes& s, long i) {
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < PQ3D_INSTANCE_MAX_SCENES; ++k) b += (k < s.B && i >= s.off[k]) ? 1 : 0;
-  return b;
-}
 
 __global__ __launch_bounds__(256) void it_init_kernel(int* __restrict__ first, long nfirst, int64_t* __restrict__ labels, long nlab,
                                                       int* __restrict__ n_inst, int* __restrict__ seg_len, int B,
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(256) void it_first_kernel(const int64_t* __restrict
   const bool live = i < P;
   int b = -1, top = 0, e = 0;
   if (live) {
-    b = it_scene(sc, i);
+    b = sc.scene(i);
     const int slot = pq_it_slot(p2i[i], IT_CAP);
     if (slot < 0) e |= 1;
     else {
@@ -91,29 +82,11 @@ __global__ __launch_bounds__(256) void it_first_kernel(const int64_t* __restrict
   }
 }
 
-// exclusive scan of one int per thread over the IT_NT threads of a block; `total` = the block's sum.  lds: IT_NT / 64 ints.
-PQ_DEV int it_block_scan(int v, int* lds, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < IT_NT / 64; ++w) { const int c = lds[w]; tot += c; if (w < wave) base += c; }
-  total = tot;
-  return base + x - v;
-}
-
 __global__ __launch_bounds__(IT_NT) void it_rank_kernel(const int64_t* __restrict__ p2sem, ItScenes sc, ItFilter fl, int max_rows,
                                                         const int* __restrict__ first, int* __restrict__ rank,
                                                         int64_t* __restrict__ ids, int64_t* __restrict__ labels,
                                                         int* __restrict__ n_inst, int* __restrict__ err) {
-  __shared__ int lds[IT_NT / 64];
+  __shared__ int lds[SCAN_LDS];
   const int b = blockIdx.x, k0 = threadIdx.x * IT_PER;
   const long long n = sc.off[b + 1] - sc.off[b];
   bool keep[IT_PER];
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(IT_NT) void it_rank_kernel(const int64_t* __restric
     c += keep[j] ? 1 : 0;
   }
   int total;
-  int r = it_block_scan(c, lds, total);
+  int r = block_excl_scan(c, lds, total);
 #pragma unroll
   for (int j = 0; j < IT_PER; ++j) {
     const int k = k0 + j;
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(256) void it_cells_kernel(const int64_t* __restrict
                                                        uint8_t* __restrict__ segmask, int16_t* __restrict__ prank) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  const int b = it_scene(sc, i);
+  const int b = sc.scene(i);
   const int slot = pq_it_slot(p2i[i], IT_CAP);
   int r = slot < 0 ? -1 : rank[(long)b * IT_SLOTS + slot];
   if (r >= mk.rows[b]) r = -1;
@@ -181,7 +154,7 @@ __global__ __launch_bounds__(256) void it_cells_padded_kernel(const int64_t* __r
                                                               unsigned* __restrict__ T, int* __restrict__ cnt) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  const int b = it_scene(sc, i);
+  const int b = sc.scene(i);
   const int slot = pq_it_slot(p2i[i], IT_CAP);
   if (slot < 0) return;
   const int r = rank[(long)b * IT_SLOTS + slot];
@@ -203,9 +176,7 @@ __global__ __launch_bounds__(256) void it_count_kernel(const int* __restrict__ c
 // unaligned 16-byte copies; the scene's last, partial chunk goes out as bytes.
 __global__ __launch_bounds__(256) void it_full_kernel(ItScenes sc, ItMasks mk, const int16_t* __restrict__ prank,
                                                       uint8_t* __restrict__ out) {
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < PQ3D_INSTANCE_MAX_SCENES; ++k) b += (k < sc.B && (int)blockIdx.x >= mk.blk0[k]) ? 1 : 0;
+  const int b = ragged_find(mk.blk0, sc.B, (int)blockIdx.x);
   const long long Pb = sc.off[b + 1] - sc.off[b], G = mk.rows[b];
   const long long p = ((long long)((int)blockIdx.x - mk.blk0[b]) * 256 + threadIdx.x) * FM_PTS;
   const long long g0 = (long long)blockIdx.y * FM_ROWS, g1 = min(g0 + FM_ROWS, G);
@@ -232,19 +203,10 @@ __global__ __launch_bounds__(256) void it_full_kernel(ItScenes sc, ItMasks mk, c
   }
 }
 
-// host: scene table from the caller's offsets; 0 or an argument error text
-const char* it_table(const int64_t* offsets, int B, ItScenes& sc) {
-  if (!offsets || B < 1 || B > PQ3D_INSTANCE_MAX_SCENES) return "instance targets: 1 <= B <= PQ3D_INSTANCE_MAX_SCENES scenes, offsets a host array";
-  if (offsets[0] != 0) return "instance targets: offsets[0] must be 0";
-  for (int b = 0; b < B; ++b)
-    if (offsets[b + 1] <= offsets[b]) return "instance targets: every scene needs at least one point";
-  if (offsets[B] > PQ3D_VOXELIZE_MAX_POINTS) return "instance targets: at most PQ3D_VOXELIZE_MAX_POINTS points per call";
-  sc.B = B;
-  for (int b = 0; b <= PQ3D_INSTANCE_MAX_SCENES; ++b) sc.off[b] = offsets[b < B ? b : B];
-  return nullptr;
-}
-
 }  // namespace
+
+// host: the scene table from an entry point's `offsets` and `B`, or its argument error
+#define IT_TABLE(sc, who) PQ_SCENE_TABLE(sc, offsets, B, PQ3D_VOXELIZE_MAX_POINTS, PQ3D_VOXELIZE_MAX_POINTS, who)
 
 extern "C" int pq3d_instance_tables(const int64_t* point2instance, const int64_t* point2semantic, const int64_t* point2segment,
                                     const int64_t* offsets, int32_t B, const int64_t* filter, int32_t n_filter, int64_t seg_limit,
@@ -254,7 +216,7 @@ extern "C" int pq3d_instance_tables(const int64_t* point2instance, const int64_t
   PQ_CHECK_ARG(point2instance && point2semantic && point2segment && first && rank && labels && n_inst && seg_len && err,
                "pq3d_instance_tables: null pointer");
   ItScenes sc;
-  if (const char* e = it_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  IT_TABLE(sc, "pq3d_instance_tables");
   PQ_CHECK_ARG(n_filter >= 0 && n_filter <= PQ3D_INSTANCE_MAX_FILTER && (n_filter == 0 || filter),
                "pq3d_instance_tables: 0 <= n_filter <= PQ3D_INSTANCE_MAX_FILTER classes, filter a host array");
   PQ_CHECK_ARG(seg_limit >= 1 && seg_limit <= PQ3D_INSTANCE_MAX_SEGMENTS, "pq3d_instance_tables: 1 <= seg_limit <= PQ3D_INSTANCE_MAX_SEGMENTS");
@@ -281,7 +243,7 @@ extern "C" int pq3d_instance_masks(const int64_t* point2instance, const int64_t*
   PQ_CHECK_ARG(point2instance && point2segment && rank && rows && cols, "pq3d_instance_masks: null pointer");
   PQ_CHECK_ARG((prank != nullptr) == (full_masks != nullptr), "pq3d_instance_masks: full_masks and prank go together");
   ItScenes sc;
-  if (const char* e = it_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  IT_TABLE(sc, "pq3d_instance_masks");
   ItMasks mk = {};
   long long moff = 0, foff = 0, poff = 0, gmax = 0;
   int blk = 0;
@@ -315,7 +277,7 @@ extern "C" int pq3d_instance_masks_padded(const int64_t* point2instance, const i
   PQ_DEVICE_GUARD(stream, point2instance);
   PQ_CHECK_ARG(point2instance && point2segment && rank && T && cnt && t_sum, "pq3d_instance_masks_padded: null pointer");
   ItScenes sc;
-  if (const char* e = it_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  IT_TABLE(sc, "pq3d_instance_masks_padded");
   PQ_CHECK_ARG(Ns >= 1 && Ns <= PQ3D_INSTANCE_MAX_SEGMENTS && Nt >= 1 && Nt <= PQ3D_INSTANCE_MAX_IDS,
                "pq3d_instance_masks_padded: 1 <= Ns <= PQ3D_INSTANCE_MAX_SEGMENTS, 1 <= Nt <= PQ3D_INSTANCE_MAX_IDS");
   const long P = (long)offsets[B], rows = (long)B * Nt;

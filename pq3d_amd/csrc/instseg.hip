@@ -31,6 +31,7 @@
 //                          record_preds :326-339), reduced by instseg_box_kernel.
 // Every sum runs in a fixed order (no float atomics): results are bit-identical run to run.
 #include "common.h"
+#include "ragged.h"
 
 namespace {
 
@@ -45,42 +46,6 @@ struct BoxPart {          // 64 bytes
   int pad[3];
 };
 static_assert(sizeof(BoxPart) == PQ3D_INSTSEG_BOX_PART_BYTES, "box partial layout");
-
-// largest b in [0, B) with off[b] <= i (i < off[B]): the scene of row i of a concatenation
-PQ_DEV int scene_of(const int64_t* __restrict__ off, int B, long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-PQ_DEV int wave_incl_scan_i(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-// exclusive prefix of v over the block (<= 1024 threads); *total = block sum.  sm: >= 17 ints of LDS.
-PQ_DEV int block_excl_scan_i(int v, int* sm, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  const int inc = wave_incl_scan_i(v);
-  __syncthreads();
-  if (lane == 63) sm[w] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int i = 0; i < nw; ++i) { const int t = sm[i]; sm[i] = s; s += t; }
-    sm[16] = s;
-  }
-  __syncthreads();
-  *total = sm[16];
-  return inc - v + sm[w];
-}
 
 // ascending bitonic sort of keys[0, n) in LDS (n a power of two <= 1024, 1024 threads)
 PQ_DEV void bitonic_sort_u64(unsigned long long* keys, int n) {
@@ -104,8 +69,6 @@ PQ_DEV int pow2_ceil(int n) {
   while (p < n) p <<= 1;
   return p;
 }
-
-PQ_DEV float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- 1. range checks + voxels per segment ------------------------------------------------------------------------------
 // stats[0] |= 1: a voxel2segment id outside [0, S);  2: a voxel_to_full_maps id outside [0, V_b);  4: a negative
@@ -231,7 +194,7 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
                                                             const int* __restrict__ qvalid, int kall, int* __restrict__ kout) {
   __shared__ unsigned long long keys[MAX_K];
   __shared__ int hist[256];
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   __shared__ int pick[2];
   const int b = blockIdx.x, tid = threadIdx.x;
   const long base0 = RAGGED ? (long)seg[b] : (long)b * n;
@@ -244,7 +207,7 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
     for (int r0 = 0; r0 < rows; r0 += 1024) {
       const int r = r0 + tid;
       int tot;
-      (void)block_excl_scan_i(r < rows && (!qvalid || qvalid[base0 / C + r]) ? 1 : 0, sm, &tot);
+      (void)block_excl_scan(r < rows && (!qvalid || qvalid[base0 / C + r]) ? 1 : 0, sm, tot);
       kept += tot;
     }
     const long kc = (long)kept * C;
@@ -307,7 +270,7 @@ __global__ __launch_bounds__(1024) void instseg_topk_kernel(const float* __restr
   for_each([&](int i, unsigned u) {
     const int gt = i < n && u > T, eq = i < n && u == T;
     int tot;
-    const int ex = block_excl_scan_i(gt | (eq << 16), sm, &tot);   // <= 1024 per tile: both counts fit 16 bits
+    const int ex = block_excl_scan(gt | (eq << 16), sm, tot);   // <= 1024 per tile: both counts fit 16 bits
     if (gt) {
       const int slot = gt_carry + (ex & 0xffff);     // < n_gt by construction of T; the test only guards the LDS array
       if (slot < n_gt) keys[slot] = cand_key(u, i);
@@ -588,12 +551,6 @@ __global__ __launch_bounds__(256) void instseg_gt_part_kernel(const unsigned cha
     o.pad[0] = o.pad[1] = o.pad[2] = 0;
     part[cid] = o;
   }
-}
-
-inline unsigned grid_cap(long n, long per) {
-  long g = (n + per - 1) / per;
-  if (g > 2048) g = 2048;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 
 }  // namespace

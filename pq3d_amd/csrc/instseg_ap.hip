@@ -22,6 +22,7 @@
 //                     void [K] (the void group's row) and pred_verts [K] (the column's points: void + every group).
 // Every count is an exact integer: results are bit-identical run to run.  Each mask byte is read once (ap_count_kernel).
 #include "common.h"
+#include "ragged.h"
 #include "segment_plan.h"
 
 namespace {
@@ -29,37 +30,6 @@ namespace {
 using namespace pq3d_plan;
 
 constexpr int INST = PQ3D_AP_INST;
-
-PQ_DEV int scene_of(const int64_t* __restrict__ off, int B, long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// exclusive prefix of v over the block (<= 1024 threads); *total = block sum.  sm: >= 17 ints of LDS.
-PQ_DEV int block_excl_scan(int v, int* sm, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(inc, d);
-    if (lane >= d) inc += u;
-  }
-  __syncthreads();
-  if (lane == 63) sm[w] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int i = 0; i < nw; ++i) { const int t = sm[i]; sm[i] = s; s += t; }
-    sm[16] = s;
-  }
-  __syncthreads();
-  *total = sm[16];
-  return inc - v + sm[w];
-}
 
 // ---- 1. local keys + presence bits --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ap_mark_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ poff, int B,
@@ -93,7 +63,7 @@ __global__ __launch_bounds__(256) void ap_mark_kernel(const int64_t* __restrict_
 // ---- 2. per scene: word prefix counts of the bit map, G_b ------------------------------------------------------------
 __global__ __launch_bounds__(1024) void ap_rank_kernel(const unsigned* __restrict__ bits, long W, int* __restrict__ wpre,
                                                        int64_t* __restrict__ sizes) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   const int b = blockIdx.x, tid = threadIdx.x;
   const long per = (W + 1023) / 1024;
   const long w0 = min(W, tid * per), w1 = min(W, w0 + per);
@@ -101,7 +71,7 @@ __global__ __launch_bounds__(1024) void ap_rank_kernel(const unsigned* __restric
   int n = 0;
   for (long w = w0; w < w1; ++w) n += __popc(bw[w]);
   int total;
-  int run = block_excl_scan(n, sm, &total);
+  int run = block_excl_scan(n, sm, total);
   for (long w = w0; w < w1; ++w) {
     wpre[(long)b * W + w] = run;
     run += __popc(bw[w]);
@@ -249,12 +219,6 @@ __global__ __launch_bounds__(256) void ap_pack_kernel(const int* __restrict__ ou
       dst[e + K] = s;
     }
   }
-}
-
-inline unsigned grid_cap(long n, long per) {
-  long g = (n + per - 1) / per;
-  if (g > 2048) g = 2048;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 
 }  // namespace

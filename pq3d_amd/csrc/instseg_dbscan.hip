@@ -32,6 +32,7 @@
 // The partition is unique, so the columns do not depend on the order the unions ran in; every sum runs in a fixed order
 // (no float atomics): results are bit-identical run to run.
 #include "common.h"
+#include "ragged.h"
 #include "segment_plan.h"
 
 namespace {
@@ -43,15 +44,6 @@ constexpr int NODE_SPAN = 128;    // sorted voxels per wave of the node kernel
 constexpr int VCHUNK = PQ3D_INSTSEG_SEG_CHUNK;   // voxels per partial-sum chunk of the table kernel
 constexpr int GRID_WORDS = PQ3D_DBSCAN_GRID_WORDS;
 constexpr int NONE = 0x7fffffff;  // minvox of a node without mask voxels
-
-PQ_DEV int scene_of(const int64_t* __restrict__ off, int B, long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // order-preserving unsigned code of a float (larger float -> larger code)
 PQ_DEV unsigned fenc(float f) {
@@ -93,32 +85,6 @@ PQ_DEV bool within(double ax, double ay, double az, double bx, double by, double
   const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
   return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)) <= eps2;
 }
-
-// exclusive prefix of v over the block (<= 1024 threads); *total = block sum.  sm: >= 17 longs of LDS.
-PQ_DEV long block_excl_scan_l(long v, long* sm, long* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  long inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long u = __shfl_up(inc, d);
-    if (lane >= d) inc += u;
-  }
-  __syncthreads();
-  if (lane == 63) sm[w] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long s = 0;
-    for (int i = 0; i < nw; ++i) { const long t = sm[i]; sm[i] = s; s += t; }
-    sm[16] = s;
-  }
-  __syncthreads();
-  *total = sm[16];
-  const long r = inc - v + sm[w];
-  __syncthreads();
-  return r;
-}
-
-PQ_DEV float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- bounds: grid (16, B); bounds[b*6 + d] = ~code(min), [b*6 + 3 + d] = code(max) (both maxima, so zero is the identity)
 __global__ __launch_bounds__(256) void dbscan_bounds_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ voff,
@@ -206,17 +172,17 @@ __global__ __launch_bounds__(1024) void dbscan_cells_kernel(const int64_t* __res
                                                             const float* __restrict__ xyz, long NV, const int* __restrict__ tile_cnt,
                                                             int* __restrict__ cell_first, int* __restrict__ cell_of_voxel,
                                                             float4* __restrict__ sxyz, int* __restrict__ meta) {
-  __shared__ long sm[17];
+  __shared__ long sm[SCAN_LDS];
   const int t = blockIdx.x, tid = threadIdx.x;
   long pre = 0;
   for (int u = tid; u < t; u += 1024) pre += tile_cnt[u];
   long base;
-  (void)block_excl_scan_l(pre, sm, &base);
+  (void)block_excl_scan(pre, sm, base);
   const long i = (long)t * TILE + tid;
   const bool in = i < NV;
   const bool s = in && cell_start(key, perm, i);
   long tot;
-  const long ex = block_excl_scan_l(s ? 1 : 0, sm, &tot);
+  const long ex = block_excl_scan(s ? 1L : 0L, sm, tot);
   const long c = base + ex + (s ? 1 : 0) - 1;               // cells started at or before i, minus one
   if (in) {
     const int v = perm[i];
@@ -391,14 +357,14 @@ PQ_DEV long hrank(const unsigned long long* __restrict__ hb, const int* __restri
 __global__ __launch_bounds__(1024) void dbscan_prefix_kernel(const unsigned long long* __restrict__ hb, long WV,
                                                              const int64_t* __restrict__ voff, int B, int Q,
                                                              int* __restrict__ pre, int* __restrict__ cnt) {
-  __shared__ long sm[17];
+  __shared__ long sm[SCAN_LDS];
   const int q = blockIdx.x, tid = threadIdx.x;
   long carry = 0;
   for (long w0 = 0; w0 < WV; w0 += 1024) {
     const long w = w0 + tid;
     const long c = w < WV ? __popcll(hb[(long)q * WV + w]) : 0;
     long tot;
-    const long ex = block_excl_scan_l(c, sm, &tot);
+    const long ex = block_excl_scan(c, sm, tot);
     if (w < WV) pre[(long)q * WV + w] = (int)(carry + ex);
     carry += tot;
   }
@@ -410,14 +376,14 @@ __global__ __launch_bounds__(1024) void dbscan_prefix_kernel(const unsigned long
 // ---- one workgroup: colq[b * Q + q] = first column of (b, q); colseg[b] = first column of scene b (colseg[B] = total)
 __global__ __launch_bounds__(1024) void dbscan_colofs_kernel(const int* __restrict__ cnt, int B, int Q, int* __restrict__ colq,
                                                              int64_t* __restrict__ colseg) {
-  __shared__ long sm[17];
+  __shared__ long sm[SCAN_LDS];
   long base = 0;
   for (int b = 0; b < B; ++b) {
     if (threadIdx.x == 0) colseg[b] = base;
     for (int q0 = 0; q0 < Q; q0 += 1024) {
       const int q = q0 + threadIdx.x;
       long tot;
-      const long ex = block_excl_scan_l(q < Q ? cnt[(long)b * Q + q] : 0, sm, &tot);
+      const long ex = block_excl_scan(q < Q ? (long)cnt[(long)b * Q + q] : 0L, sm, tot);
       if (q < Q) colq[(long)b * Q + q] = (int)(base + ex);
       base += tot;
     }
@@ -500,11 +466,6 @@ __global__ __launch_bounds__(256) void dbscan_table_kernel(const float* __restri
   }
 }
 
-inline unsigned grid_cap(long n, long per) {
-  long g = (n + per - 1) / per;
-  if (g > 2048) g = 2048;
-  return (unsigned)(g < 1 ? 1 : g);
-}
 
 // workspace sections, 256-byte aligned, in this order (pq3d_dbscan_ws_bytes)
 struct DbWs {

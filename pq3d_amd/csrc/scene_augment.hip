@@ -10,6 +10,7 @@
 // -ffp-contract=off and no fast-math); a stage that is off is skipped, not fed a neutral value.
 // The scene tables (row offsets, first block of every scene) are host arrays: they travel by value as kernel arguments.
 #include "common.h"
+#include "ragged.h"
 
 #include <float.h>
 #include <math.h>
@@ -23,19 +24,10 @@ constexpr int AUG_GROUP = 4;                        // consecutive points per th
 constexpr int AUG_MAXB = PQ3D_VOXELIZE_MAX_SCENES;
 static_assert(sizeof(pq3d_scene_augment_params) == PQ3D_SCENE_AUGMENT_K * sizeof(float), "parameter row");
 
-struct AugScenes {
-  int B;
-  long long off[AUG_MAXB + 1];     // points of scene b: [off[b], off[b+1]); entries past B repeat off[B]
+struct AugScenes : SceneTable<AUG_MAXB> {     // off: points of scene b
   int blk0[AUG_MAXB + 1];          // first statistics block of scene b; blk0[B] = all blocks
 };
 struct AugColor { float mean255[3], rstd255[3]; };
-
-PQ_DEV int aug_scene(const AugScenes& s, long i) {
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < AUG_MAXB; ++k) b += (k < s.B && i >= s.off[k]) ? 1 : 0;
-  return b;
-}
 
 // workspace: sums [nblk][3] fp64, then minima [nblk][3] and maxima [nblk][3] fp32
 PQ_DEV const float* aug_ws_min(const void* ws, int nblk) { return (const float*)((const double*)ws + (long)nblk * 3); }
@@ -48,9 +40,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_stats_kernel(const float* __restri
   if (!train) return;                                        // uniform
   const int nblk = sc.blk0[sc.B], blk = blockIdx.x;
   if (blk >= nblk) return;
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < AUG_MAXB; ++k) b += (k < sc.B && blk >= sc.blk0[k]) ? 1 : 0;
+  const int b = ragged_find(sc.blk0, sc.B, blk);
   const long p0 = sc.off[b] + (long)(blk - sc.blk0[b]) * AUG_BLOCK, p1 = sc.off[b + 1];
   double s[3] = {0.0, 0.0, 0.0};
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(const float* xyz, con
   const long P = sc.off[sc.B];
   const long g0 = (long)blockIdx.x * (AUG_NT * AUG_GROUP);                 // first point of the workgroup (< P by the grid)
   const long g1 = g0 + AUG_NT * AUG_GROUP < P ? g0 + AUG_NT * AUG_GROUP : P;
-  const int b_lo = aug_scene(sc, g0), b_hi = aug_scene(sc, g1 - 1), nsc = b_hi - b_lo + 1;
+  const int b_lo = sc.scene(g0), b_hi = sc.scene(g1 - 1), nsc = b_hi - b_lo + 1;
   const int tid = threadIdx.x;
   // the parameter rows of the workgroup's scenes (zeros = every stage off in evaluation)
   for (int t = tid; t < nsc * PQ3D_SCENE_AUGMENT_K; t += AUG_NT) {
@@ -188,19 +178,19 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(const float* xyz, con
   const long i0 = g0 + (long)tid * AUG_GROUP;
   if (i0 >= P) return;
   int e = 0;
-  const int b0 = aug_scene(sc, i0);
+  const int b0 = sc.scene(i0);
   if (VEC && i0 + AUG_GROUP <= P) {
     float4 xi[3], ci[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) { xi[j] = ((const float4*)(xyz + i0 * 3))[j]; ci[j] = ((const float4*)(rgb + i0 * 3))[j]; }
     float* xf = (float*)xi;
     float* cf = (float*)ci;
-    const int b3 = aug_scene(sc, i0 + AUG_GROUP - 1);
+    const int b3 = sc.scene(i0 + AUG_GROUP - 1);
     float4 fo[6];
     float* ff = (float*)fo;
 #pragma unroll
     for (int j = 0; j < AUG_GROUP; ++j) {
-      const int b = b3 == b0 ? b0 : aug_scene(sc, i0 + j);       // a group that straddles scenes: every point its own
+      const int b = b3 == b0 ? b0 : sc.scene(i0 + j);            // a group that straddles scenes: every point its own
       float x[3] = {xf[j * 3], xf[j * 3 + 1], xf[j * 3 + 2]}, c[3] = {cf[j * 3], cf[j * 3 + 1], cf[j * 3 + 2]};
       e |= aug_point(kc[b], cc, x, c);
 #pragma unroll
@@ -212,7 +202,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(const float* xyz, con
     for (int j = 0; j < 6; ++j) ((float4*)(feat_out + i0 * 6))[j] = fo[j];
   } else {
     for (long i = i0; i < i0 + AUG_GROUP && i < P; ++i) {        // the batch's tail, or unaligned arrays: point by point
-      const int b = aug_scene(sc, i);
+      const int b = sc.scene(i);
       float x[3] = {xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]}, c[3] = {rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]};
       e |= aug_point(kc[b], cc, x, c);
 #pragma unroll
@@ -222,21 +212,16 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(const float* xyz, con
   if (e) atomicOr(err, e);       // (integer OR: the word does not depend on the order)
 }
 
-// host: scene table from the caller's offsets; 0 or an argument error text
-const char* aug_table(const int64_t* offsets, int B, AugScenes& sc) {
-  if (!offsets || B < 1 || B > AUG_MAXB) return "pq3d_scene_augment: 1 <= B <= PQ3D_VOXELIZE_MAX_SCENES scenes, offsets a host array";
-  if (offsets[0] != 0) return "pq3d_scene_augment: offsets[0] must be 0";
-  for (int b = 0; b < B; ++b)
-    if (offsets[b + 1] <= offsets[b]) return "pq3d_scene_augment: every scene needs at least one point";
-  if (offsets[B] > PQ3D_VOXELIZE_MAX_POINTS) return "pq3d_scene_augment: at most PQ3D_VOXELIZE_MAX_POINTS points per call";
-  sc.B = B;
+// host: scene table from the caller's offsets; "" or an argument error text
+std::string aug_table(const int64_t* offsets, int B, AugScenes& sc) {
+  const std::string e = scene_table_fill(sc, offsets, B, PQ3D_VOXELIZE_MAX_POINTS, PQ3D_VOXELIZE_MAX_POINTS, "pq3d_scene_augment");
+  if (!e.empty()) return e;
   int blk = 0;
   for (int b = 0; b <= AUG_MAXB; ++b) {
-    sc.off[b] = offsets[b < B ? b : B];
     sc.blk0[b] = blk;
-    if (b < B) blk += (int)((offsets[b + 1] - offsets[b] + AUG_BLOCK - 1) / AUG_BLOCK);
+    if (b < B) blk += (int)((sc.off[b + 1] - sc.off[b] + AUG_BLOCK - 1) / AUG_BLOCK);
   }
-  return nullptr;
+  return e;
 }
 
 long long aug_ws_bytes(const AugScenes& sc) { return (long long)sc.blk0[sc.B] * (3 * 8 + 6 * 4); }
@@ -245,7 +230,8 @@ long long aug_ws_bytes(const AugScenes& sc) { return (long long)sc.blk0[sc.B] * 
 
 extern "C" int64_t pq3d_scene_augment_ws_bytes(const int64_t* offsets, int32_t B) {
   AugScenes sc;
-  if (const char* e = aug_table(offsets, B, sc)) { pq3d_set_error(e); return -1; }
+  const std::string e = aug_table(offsets, B, sc);
+  if (!e.empty()) { pq3d_set_error(e.c_str()); return -1; }
   return aug_ws_bytes(sc);
 }
 
@@ -254,7 +240,8 @@ extern "C" int pq3d_scene_augment_stats(const float* coordinates, const int64_t*
   PQ_DEVICE_GUARD(stream, coordinates);
   PQ_CHECK_ARG(coordinates && err, "pq3d_scene_augment_stats: null pointer");
   AugScenes sc;
-  if (const char* e = aug_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  const std::string e = aug_table(offsets, B, sc);
+  PQ_CHECK_ARG(e.empty(), e.c_str());
   if (train) {
     PQ_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ws_bytes >= aug_ws_bytes(sc),
                  "pq3d_scene_augment_stats: workspace missing, unaligned or smaller than pq3d_scene_augment_ws_bytes");
@@ -271,7 +258,8 @@ extern "C" int pq3d_scene_augment_apply(const float* coordinates, const float* c
   PQ_DEVICE_GUARD(stream, coordinates);
   PQ_CHECK_ARG(coordinates && colors && color_consts && coordinates_out && features_out && err, "pq3d_scene_augment_apply: null pointer");
   AugScenes sc;
-  if (const char* e = aug_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  const std::string e = aug_table(offsets, B, sc);
+  PQ_CHECK_ARG(e.empty(), e.c_str());
   if (params) {
     PQ_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && ws_bytes >= aug_ws_bytes(sc),
                  "pq3d_scene_augment_apply: workspace missing, unaligned or smaller than pq3d_scene_augment_ws_bytes");

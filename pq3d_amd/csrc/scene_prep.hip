@@ -11,6 +11,7 @@
 //     change.
 // The scene tables (row offsets) are host arrays: they travel to the kernels by value as kernel arguments.
 #include "common.h"
+#include "ragged.h"
 
 #include <float.h>
 #include <limits.h>
@@ -24,17 +25,7 @@ constexpr int VOX_QLIM = VOX_BIAS - 8;           // CoordPyramid's range: -2^19 
 constexpr int VOX_ITEMS = PQ3D_VOXELIZE_BLOCK / 256;   // consecutive points per thread of the count / emit kernels
 constexpr unsigned long long VOX_EMPTY = ~0ull;  // no packed key has bit 63 set (scene < 8)
 
-struct VoxScenes {
-  int B;
-  long long off[PQ3D_VOXELIZE_MAX_SCENES + 1];
-};
-
-PQ_DEV int vox_scene(const VoxScenes& s, long i) {
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < PQ3D_VOXELIZE_MAX_SCENES; ++k) b += (k < s.B && i >= s.off[k]) ? 1 : 0;
-  return b;
-}
+typedef SceneTable<PQ3D_VOXELIZE_MAX_SCENES> VoxScenes;
 
 // q = floor(x / vs): IEEE division (the build has no fast-math and -ffp-contract=off; x * (1 / vs) differs on lattice points).
 // Returns 0 or the error bits: 1 non-finite, 2 outside [-VOX_QLIM, VOX_QLIM).
@@ -75,7 +66,7 @@ __global__ __launch_bounds__(256) void vox_insert_kernel(const float* __restrict
   int q[3];
   const int e = vox_quantize(xyz + i * 3, vs, q);
   if (e) { atomicOr(err, e); slot[i] = -1; return; }
-  const unsigned long long key = vox_pack(vox_scene(sc, i), q);
+  const unsigned long long key = vox_pack(sc.scene(i), q);
   unsigned h = vox_hash(key) & mask;
   int found = -1;
   // the table holds at most P <= (mask + 1) / 2 keys, so a free or matching slot exists; the probe count is bounded anyway
@@ -89,25 +80,6 @@ __global__ __launch_bounds__(256) void vox_insert_kernel(const float* __restrict
   else atomicOr(err, 4);
 }
 
-// exclusive scan of one int per thread over a block of NT threads; `total` = the block's sum.  lds: NT / 64 ints.
-template <int NT> PQ_DEV int block_excl_scan(int v, int* lds, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) { const int c = lds[w]; tot += c; if (w < wave) base += c; }
-  __syncthreads();
-  total = tot;
-  return base + x - v;
-}
-
 PQ_DEV bool vox_is_rep(const int* __restrict__ slot, const int* __restrict__ rep, long i) {
   const int s = slot[i];
   return s >= 0 && rep[s] == (int)i;
@@ -115,25 +87,25 @@ PQ_DEV bool vox_is_rep(const int* __restrict__ slot, const int* __restrict__ rep
 
 __global__ __launch_bounds__(256) void vox_count_kernel(const int* __restrict__ slot, const int* __restrict__ rep, long P,
                                                         int* __restrict__ bsum) {
-  __shared__ int lds[4];
+  __shared__ int lds[SCAN_LDS];
   const long i0 = (long)blockIdx.x * PQ3D_VOXELIZE_BLOCK + (long)threadIdx.x * VOX_ITEMS;
   int c = 0;
 #pragma unroll
   for (int j = 0; j < VOX_ITEMS; ++j)
     if (i0 + j < P) c += vox_is_rep(slot, rep, i0 + j) ? 1 : 0;
   int total;
-  block_excl_scan<256>(c, lds, total);
+  block_excl_scan(c, lds, total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // one workgroup: bsum[0 .. nblk) -> its exclusive prefix sums in place; meta[B] = the number of voxels
 __global__ __launch_bounds__(1024) void vox_scan_kernel(int* __restrict__ bsum, int nblk, long long* __restrict__ meta, int B) {
-  __shared__ int lds[16];
+  __shared__ int lds[SCAN_LDS];
   const int per = (nblk + 1023) / 1024, k0 = threadIdx.x * per, k1 = min(k0 + per, nblk);
   int c = 0;
   for (int k = k0; k < k1; ++k) c += bsum[k];
   int total;
-  int run = block_excl_scan<1024>(c, lds, total);
+  int run = block_excl_scan(c, lds, total);
   for (int k = k0; k < k1; ++k) { const int v = bsum[k]; bsum[k] = run; run += v; }
   if (threadIdx.x == 0) meta[B] = total;
 }
@@ -143,7 +115,7 @@ __global__ __launch_bounds__(256) void vox_emit_kernel(const float* __restrict__
                                                        const int* __restrict__ bpre, int* __restrict__ pv,
                                                        int64_t* __restrict__ unique_map, int32_t* __restrict__ vcoord,
                                                        long long* __restrict__ meta) {
-  __shared__ int lds[4];
+  __shared__ int lds[SCAN_LDS];
   const long i0 = (long)blockIdx.x * PQ3D_VOXELIZE_BLOCK + (long)threadIdx.x * VOX_ITEMS;
   bool f[VOX_ITEMS];
   int c = 0;
@@ -153,12 +125,12 @@ __global__ __launch_bounds__(256) void vox_emit_kernel(const float* __restrict__
     c += f[j] ? 1 : 0;
   }
   int total;
-  int vid = bpre[blockIdx.x] + block_excl_scan<256>(c, lds, total);
+  int vid = bpre[blockIdx.x] + block_excl_scan(c, lds, total);
 #pragma unroll
   for (int j = 0; j < VOX_ITEMS; ++j) {
     const long i = i0 + j;
     if (i >= P) break;
-    const int b = vox_scene(sc, i);
+    const int b = sc.scene(i);
     if (i == sc.off[b]) meta[b] = vid;      // the first point of a scene is the representative of the scene's first voxel
     if (f[j]) {
       int q[3] = {0, 0, 0};
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(256) void vox_inverse_kernel(VoxScenes sc, long P, 
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
   const int s = slot[i];
-  inverse_map[i] = s < 0 ? -1 : (int64_t)pv[rep[s]] - meta[vox_scene(sc, i)];
+  inverse_map[i] = s < 0 ? -1 : (int64_t)pv[rep[s]] - meta[sc.scene(i)];
 }
 
 // ----------------------------------------------------------------------------------------------------------------- FPS
@@ -186,9 +158,8 @@ constexpr int FPS_NT = 1024, FPS_NW = FPS_NT / 64;
 constexpr int FPS_MAX_TILES = 1024;      // one tile per thread of the scene's workgroup
 constexpr int FPS_TILE_SMALL = 256, FPS_TILE_BIG = 1024;     // rows per tile: N <= 2^18 / N <= 2^20
 
-struct FpsScenes {
-  int B, T;
-  long long off[PQ3D_FPS_MAX_SCENES + 1];      // caller rows of scene b: [off[b], off[b+1])
+struct FpsScenes : SceneTable<PQ3D_FPS_MAX_SCENES> {     // off: caller rows of scene b
+  int T;                                       // rows per tile
   int row0[PQ3D_FPS_MAX_SCENES + 1];           // first workspace row of scene b (a multiple of T); row0[B] = all rows
 };
 
@@ -234,19 +205,13 @@ PQ_DEV unsigned fps_spread3(unsigned v) {     // 10 bits -> every third bit
   return v;
 }
 
-PQ_DEV int fps_scene_of(const FpsScenes& s, long i) {
-  int b = 0;
-  while (b + 1 < s.B && i >= s.off[b + 1]) ++b;
-  return b;
-}
-
 // sort key of caller row i: scene, then the 30-bit Morton code of its position in the scene's bounding box.  The key only
 // decides which rows share a tile (how much the pruning saves), never a result.
 __global__ __launch_bounds__(256) void fps_key_kernel(const float* __restrict__ pts, FpsScenes sc, const float* __restrict__ bbox,
                                                       int64_t* __restrict__ keys) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= sc.off[sc.B]) return;
-  const int b = fps_scene_of(sc, i);
+  const int b = sc.scene(i);
   unsigned code = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -443,25 +408,20 @@ __global__ __launch_bounds__(FPS_NT) void fps_scene_kernel(const float* __restri
   }
 }
 
-// host: scene table from the caller's offsets; 0 or an argument error text
-const char* fps_table(const int64_t* offsets, int B, FpsScenes& sc) {
-  if (!offsets || B < 1 || B > PQ3D_FPS_MAX_SCENES) return "pq3d_fps_scene: 1 <= B <= PQ3D_FPS_MAX_SCENES scenes, offsets a host array";
-  if (offsets[0] != 0) return "pq3d_fps_scene: offsets[0] must be 0";
+// host: scene table from the caller's offsets; "" or an argument error text
+std::string fps_table(const int64_t* offsets, int B, FpsScenes& sc) {
+  const std::string e = scene_table_fill(sc, offsets, B, PQ3D_FPS_MAX_POINTS, (long long)PQ3D_FPS_MAX_SCENES * PQ3D_FPS_MAX_POINTS,
+                                         "pq3d_fps_scene");
+  if (!e.empty()) return e;
   long long nmax = 0;
-  for (int b = 0; b < B; ++b) {
-    const long long n = offsets[b + 1] - offsets[b];
-    if (n < 1 || n > PQ3D_FPS_MAX_POINTS) return "pq3d_fps_scene: every scene needs 1 <= N <= PQ3D_FPS_MAX_POINTS points";
-    nmax = n > nmax ? n : nmax;
-  }
-  sc.B = B;
+  for (int b = 0; b < B; ++b) nmax = sc.off[b + 1] - sc.off[b] > nmax ? sc.off[b + 1] - sc.off[b] : nmax;
   sc.T = nmax <= (long long)FPS_TILE_SMALL * FPS_MAX_TILES ? FPS_TILE_SMALL : FPS_TILE_BIG;
   long long rows = 0;
   for (int b = 0; b <= PQ3D_FPS_MAX_SCENES; ++b) {
-    sc.off[b] = offsets[b < B ? b : B];
     sc.row0[b] = (int)rows;
-    if (b < B) rows += (offsets[b + 1] - offsets[b] + sc.T - 1) / sc.T * sc.T;
+    if (b < B) rows += (sc.off[b + 1] - sc.off[b] + sc.T - 1) / sc.T * sc.T;
   }
-  return nullptr;
+  return e;
 }
 
 }  // namespace
@@ -472,15 +432,10 @@ extern "C" int pq3d_voxelize(const float* coordinates, const int64_t* offsets, i
   PQ_DEVICE_GUARD(stream, coordinates);
   PQ_CHECK_ARG(coordinates && offsets && keys && rep && slot && pv && bsum && unique_map && inverse_map && voxel_coordinates && meta,
                "pq3d_voxelize: null pointer");
-  PQ_CHECK_ARG(B >= 1 && B <= PQ3D_VOXELIZE_MAX_SCENES, "pq3d_voxelize: 1 <= B <= 8 scenes (the packed key has 3 scene bits)");
   PQ_CHECK_ARG(voxel_size > 0.f && voxel_size <= FLT_MAX, "pq3d_voxelize: voxel_size must be a finite number > 0");
-  VoxScenes sc;
-  sc.B = B;
-  PQ_CHECK_ARG(offsets[0] == 0, "pq3d_voxelize: offsets[0] must be 0");
-  for (int b = 0; b <= PQ3D_VOXELIZE_MAX_SCENES; ++b) sc.off[b] = offsets[b < B ? b : B];
-  for (int b = 0; b < B; ++b) PQ_CHECK_ARG(offsets[b + 1] > offsets[b], "pq3d_voxelize: every scene needs at least one point");
-  const long P = (long)offsets[B];
-  PQ_CHECK_ARG(P <= PQ3D_VOXELIZE_MAX_POINTS, "pq3d_voxelize: at most PQ3D_VOXELIZE_MAX_POINTS points per call");
+  VoxScenes sc;      // (at most 8 scenes: the packed key has 3 scene bits)
+  PQ_SCENE_TABLE(sc, offsets, B, PQ3D_VOXELIZE_MAX_POINTS, PQ3D_VOXELIZE_MAX_POINTS, "pq3d_voxelize");
+  const long P = (long)sc.off[B];
   PQ_CHECK_ARG(capacity >= 2 * P && capacity <= (1ll << 31) && (capacity & (capacity - 1)) == 0,
                "pq3d_voxelize: capacity must be a power of two >= 2 P");
   hipStream_t s = (hipStream_t)stream;
@@ -501,7 +456,8 @@ extern "C" int pq3d_voxelize(const float* coordinates, const int64_t* offsets, i
 
 extern "C" int64_t pq3d_fps_scene_rows(const int64_t* offsets, int32_t B) {
   FpsScenes sc;
-  if (const char* e = fps_table(offsets, B, sc)) { pq3d_set_error(e); return -1; }
+  const std::string e = fps_table(offsets, B, sc);
+  if (!e.empty()) { pq3d_set_error(e.c_str()); return -1; }
   return sc.row0[B];
 }
 
@@ -509,7 +465,8 @@ extern "C" int pq3d_fps_scene_keys(const float* points, const int64_t* offsets, 
   PQ_DEVICE_GUARD(stream, points);
   PQ_CHECK_ARG(points && bbox && keys, "pq3d_fps_scene_keys: null pointer");
   FpsScenes sc;
-  if (const char* e = fps_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  const std::string e = fps_table(offsets, B, sc);
+  PQ_CHECK_ARG(e.empty(), e.c_str());
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(fps_bbox_kernel, dim3(B), dim3(FPS_NT), 0, s, points, sc, bbox);
   hipLaunchKernelGGL(fps_key_kernel, dim3((unsigned)((sc.off[B] + 255) / 256)), dim3(256), 0, s, points, sc, (const float*)bbox, keys);
@@ -523,7 +480,8 @@ extern "C" int pq3d_fps_scene(const float* points, const int64_t* offsets, int32
   PQ_DEVICE_GUARD(stream, points);
   PQ_CHECK_ARG(points && perm && ws && cidx && tilebox && idx, "pq3d_fps_scene: null pointer");
   FpsScenes sc;
-  if (const char* e = fps_table(offsets, B, sc)) { pq3d_set_error(e); return PQ3D_ERR_ARG; }
+  const std::string e = fps_table(offsets, B, sc);
+  PQ_CHECK_ARG(e.empty(), e.c_str());
   PQ_CHECK_ARG(ws_rows >= sc.row0[B], "pq3d_fps_scene: workspace smaller than pq3d_fps_scene_rows");
   for (int b = 0; b < B; ++b) {
     const long long n = offsets[b + 1] - offsets[b];

@@ -21,38 +21,12 @@
 // per voxel from the (cache-resident) segment table, streaming stores.
 // Algorithmic bytes per level: N*C*4 (rows) + N*8 (ids) + S*C*4 (result).
 #include "common.h"
+#include "ragged.h"
 #include "segment_plan.h"
 
 namespace {
 
 using namespace pq3d_plan;
-
-// ---- block-wide exclusive scan helpers (plan kernels only; not on the bandwidth path) -------------------------------
-PQ_DEV int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-// exclusive prefix of v over the block's threads (<= 1024 threads); *total = block sum.  `sm` holds >= 17 ints.
-PQ_DEV int block_excl_scan(int v, int* sm, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  const int inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane == 63) sm[w] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int i = 0; i < nw; ++i) { const int t = sm[i]; sm[i] = s; s += t; }
-    sm[16] = s;
-  }
-  __syncthreads();
-  *total = sm[16];
-  return inc - v + sm[w];
-}
 
 // ---- sort pass 1/3: keys (first pass: from the int64 ids) and per-tile digit histograms -----------------------------
 template <bool FROM_INDEX>
@@ -85,14 +59,14 @@ __global__ __launch_bounds__(256) void seg_hist_kernel(const int64_t* __restrict
 // ---- sort pass 2/3: exclusive scan of every digit's row of tile counts (one workgroup per digit) --------------------
 __global__ __launch_bounds__(256) void seg_scan_rows_kernel(int* __restrict__ tile_hist, int* __restrict__ dig_tot,
                                                             long n_tiles) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   int* row = tile_hist + (long)blockIdx.x * n_tiles;
   int carry = 0;
   for (long c0 = 0; c0 < n_tiles; c0 += 256) {
     const long i = c0 + threadIdx.x;
     const int v = i < n_tiles ? row[i] : 0;
     int tot;
-    const int ex = block_excl_scan(v, sm, &tot);
+    const int ex = block_excl_scan(v, sm, tot);
     if (i < n_tiles) row[i] = carry + ex;
     carry += tot;
   }
@@ -104,14 +78,14 @@ __global__ __launch_bounds__(256) void seg_scatter_kernel(const int* __restrict_
                                                           int* __restrict__ keys_out, int* __restrict__ perm_out,
                                                           const int* __restrict__ tile_hist, const int* __restrict__ dig_tot,
                                                           long N, int shift, long n_tiles) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   __shared__ int base[256];        // next free output slot of every digit for this tile
   __shared__ int wcnt[4][256];
   __shared__ int wbase[4][256];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   {
     int tot;
-    const int ex = block_excl_scan(dig_tot[tid], sm, &tot);
+    const int ex = block_excl_scan(dig_tot[tid], sm, tot);
     base[tid] = ex + tile_hist[(long)tid * n_tiles + blockIdx.x];
   }
   const long t0 = (long)blockIdx.x * SORT_TILE;
@@ -172,17 +146,17 @@ PQ_DEV void seg_piece_counts(const int* __restrict__ seg_off, long s, long S, in
   lg = np > 1;
 }
 __global__ __launch_bounds__(1024) void seg_piece_sums_kernel(const int* __restrict__ seg_off, int* __restrict__ bsum, long S) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   int b, n, np, lg, tp, ts, tl;
   seg_piece_counts(seg_off, (long)blockIdx.x * 1024 + threadIdx.x, S, b, n, np, lg);
-  block_excl_scan(np, sm, &tp);
-  block_excl_scan(lg ? np : 0, sm, &ts);
-  block_excl_scan(lg, sm, &tl);
+  block_excl_scan(np, sm, tp);
+  block_excl_scan(lg ? np : 0, sm, ts);
+  block_excl_scan(lg, sm, tl);
   if (threadIdx.x == 0) { bsum[3 * blockIdx.x] = tp; bsum[3 * blockIdx.x + 1] = ts; bsum[3 * blockIdx.x + 2] = tl; }
 }
 __global__ __launch_bounds__(1024) void seg_piece_blockscan_kernel(int* __restrict__ bsum, const int* __restrict__ seg_off,
                                                                    int* __restrict__ meta, long nb, long S) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   int c[3] = {0, 0, 0};
   for (long c0 = 0; c0 < nb; c0 += 1024) {
     const long i = c0 + threadIdx.x;
@@ -190,7 +164,7 @@ __global__ __launch_bounds__(1024) void seg_piece_blockscan_kernel(int* __restri
     for (int q = 0; q < 3; ++q) {
       const int v = i < nb ? bsum[3 * i + q] : 0;
       int tot;
-      const int ex = block_excl_scan(v, sm, &tot);
+      const int ex = block_excl_scan(v, sm, tot);
       if (i < nb) bsum[3 * i + q] = c[q] + ex;
       c[q] += tot;
     }
@@ -199,7 +173,7 @@ __global__ __launch_bounds__(1024) void seg_piece_blockscan_kernel(int* __restri
 }
 __global__ __launch_bounds__(1024) void seg_pieces_kernel(const int* __restrict__ seg_off, const int* __restrict__ bsum,
                                                           int4* __restrict__ pieces, int2* __restrict__ longs, long S) {
-  __shared__ int sm[17];
+  __shared__ int sm[SCAN_LDS];
   __shared__ int4 lq[1024];     // long segments of this block: {first row, rows, first piece, first slot}
   __shared__ int lseg[1024];
   __shared__ int nlq;
@@ -207,9 +181,9 @@ __global__ __launch_bounds__(1024) void seg_pieces_kernel(const int* __restrict_
   const long s = (long)blockIdx.x * 1024 + threadIdx.x;
   int b, n, np, lg, tp, ts, tl;
   seg_piece_counts(seg_off, s, S, b, n, np, lg);
-  const int ep = bsum[3 * blockIdx.x] + block_excl_scan(np, sm, &tp);
-  const int es = bsum[3 * blockIdx.x + 1] + block_excl_scan(lg ? np : 0, sm, &ts);
-  const int el = bsum[3 * blockIdx.x + 2] + block_excl_scan(lg, sm, &tl);
+  const int ep = bsum[3 * blockIdx.x] + block_excl_scan(np, sm, tp);
+  const int es = bsum[3 * blockIdx.x + 1] + block_excl_scan(lg ? np : 0, sm, ts);
+  const int el = bsum[3 * blockIdx.x + 2] + block_excl_scan(lg, sm, tl);
   constexpr int OWN = 8;        // pieces a thread writes itself; only longer segments go to the workgroup's list
   if (s < S) {
     if (!lg) {

@@ -51,18 +51,32 @@ _INSTANCE_ERRORS = {1: f"point2instance holds values outside [-1, {INSTANCE_MAX_
                     4: "a scene has more kept instances than max_instances"}
 
 
-def _scenes(ts: Sequence[torch.Tensor], what: str, max_scenes: int) -> Tuple[torch.Tensor, C.Array, List[int]]:
+def _need_device(t: torch.Tensor) -> None:
+    if not t.is_cuda:
+        raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+
+
+def _ragged(lists: Sequence[Sequence[torch.Tensor]], what: str, dtype, tail: tuple, text: str, max_points=None):
+    """Per-scene lists whose scene b holds non-empty [N_b, *tail] device tensors (the same N_b in every list): the
+    concatenation of each list, then the one host offsets array and the lengths."""
+    for ts in lists:
+        for t, t0 in zip(ts, lists[0]):
+            _need_device(t)
+            shape = (t0.shape[0] if t0.dim() else 0, *tail)
+            if t.dtype != dtype or tuple(t.shape) != shape or shape[0] < 1 or t.device != lists[0][0].device:
+                raise ValueError(f"{what}: {text}")
+    lens = [int(t.shape[0]) for t in lists[0]]
+    if max_points is not None and sum(lens) > max_points:
+        raise ValueError(f"{what}: at most {max_points} points per call, got {sum(lens)}")
+    off = (C.c_int64 * (len(lens) + 1))(0, *np.cumsum(lens).tolist())
+    return (*((ts[0] if len(ts) == 1 else torch.cat(list(ts), 0)).contiguous() for ts in lists), off, lens)
+
+
+def _scenes(ts: Sequence[torch.Tensor], what: str, max_scenes: int, max_points=None) -> Tuple[torch.Tensor, C.Array, List[int]]:
     """Concatenated fp32 [N, 3] device tensor, the host offsets array and the per-scene lengths."""
     if len(ts) < 1 or len(ts) > max_scenes:
         raise ValueError(f"{what}: between 1 and {max_scenes} scenes, got {len(ts)}")
-    for t in ts:
-        if not t.is_cuda:
-            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1 or t.device != ts[0].device:
-            raise ValueError(f"{what}: every scene is a non-empty [N, 3] fp32 tensor on one device")
-    lens = [int(t.shape[0]) for t in ts]
-    off = (C.c_int64 * (len(ts) + 1))(0, *np.cumsum(lens).tolist())
-    return (ts[0] if len(ts) == 1 else torch.cat(list(ts), 0)).contiguous(), off, lens
+    return _ragged([ts], what, torch.float32, (3,), "every scene is a non-empty [N, 3] fp32 tensor on one device", max_points)
 
 
 def voxelize(coordinates: Sequence[torch.Tensor], voxel_size: float):
@@ -70,13 +84,11 @@ def voxelize(coordinates: Sequence[torch.Tensor], voxel_size: float):
     int32 (scene, qx, qy, qz; scene after scene: sparse_collate's layout), ``unique_map`` (per scene [V_b] int64: the
     representative point of every voxel) and ``inverse_map`` (per scene [P_b] int64: the voxel of every point, local to the
     scene: ``voxel_to_full_maps``).  Non-finite or out-of-range coordinates raise ValueError."""
-    pts, off, lens = _scenes(coordinates, "voxelize", MAX_SCENES)
+    pts, off, lens = _scenes(coordinates, "voxelize", MAX_SCENES, MAX_POINTS)
     vs = float(np.float32(voxel_size))
     if not (np.isfinite(vs) and vs > 0.0):
         raise ValueError(f"voxel_size must be a finite number > 0, got {voxel_size}")
     B, P, dev = len(lens), sum(lens), pts.device
-    if P > MAX_POINTS:
-        raise ValueError(f"voxelize: at most {MAX_POINTS} points per call, got {P}")
     cap = 1 << max(1, (2 * P - 1).bit_length())
     keys = torch.empty(cap, dtype=torch.int64, device=dev)
     i32 = torch.empty(cap + 2 * P + (P + BLOCK - 1) // BLOCK, dtype=torch.int32, device=dev)
@@ -142,18 +154,7 @@ def _id_scenes(p2i, sem, seg, what: str):
     B = len(p2i)
     if B < 1 or B > INSTANCE_MAX_SCENES or len(sem) != B or len(seg) != B:
         raise ValueError(f"{what}: between 1 and {INSTANCE_MAX_SCENES} scenes, one point2instance / point2semantic / point2segment each")
-    for b in range(B):
-        for t in (p2i[b], sem[b], seg[b]):
-            if not t.is_cuda:
-                raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
-            if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] < 1 or t.shape != p2i[b].shape or t.device != p2i[0].device:
-                raise ValueError(f"{what}: every scene has three non-empty [P_b] int64 tensors on one device")
-    lens = [int(t.shape[0]) for t in p2i]
-    if sum(lens) > MAX_POINTS:
-        raise ValueError(f"{what}: at most {MAX_POINTS} points per call, got {sum(lens)}")
-    off = (C.c_int64 * (B + 1))(0, *np.cumsum(lens).tolist())
-    cat = lambda ts: (ts[0] if B == 1 else torch.cat(list(ts))).contiguous()
-    return cat(p2i), cat(sem), cat(seg), off, lens
+    return _ragged([p2i, sem, seg], what, torch.int64, (), "every scene has three non-empty [P_b] int64 tensors on one device", MAX_POINTS)
 
 
 def _filter(filter_out_classes) -> Tuple[C.c_void_p, int]:
@@ -384,18 +385,15 @@ def augment_scenes(coordinates: Sequence[torch.Tensor], colors: Sequence[torch.T
     [P, 3] and one [P, 6] tensor and the device error word [1] int32 (``check_scene_augment(err)`` reads it).  Two launches,
     no device-to-host read; the same inputs give the same bits.  ``out=(xyz [P, 3], features [P, 6])``: contiguous fp32
     buffers to write into (the static buffers of a captured step)."""
-    pts, off, lens = _scenes(coordinates, "augment_scenes", MAX_SCENES)
+    pts, off, lens = _scenes(coordinates, "augment_scenes", MAX_SCENES, MAX_POINTS)
     col, _off, clens = _scenes(colors, "augment_scenes", MAX_SCENES)
     if clens != lens or col.device != pts.device:
         raise ValueError("augment_scenes: one [P_b, 3] colors tensor per scene, matching coordinates")
     B, P, dev = len(lens), sum(lens), pts.device
-    if P > MAX_POINTS:
-        raise ValueError(f"augment_scenes: at most {MAX_POINTS} points per call, got {P}")
     if train:
         if params is None:
             raise ValueError("augment_scenes: train=True needs params (draw_scene_augment)")
-        if not params.is_cuda:
-            raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+        _need_device(params)
         if params.dtype != torch.float32 or tuple(params.shape) != (B, AUG_K) or not params.is_contiguous() or params.device != dev:
             raise ValueError(f"augment_scenes: params must be a contiguous fp32 [{B}, {AUG_K}] tensor on {dev}")
     if out is None:
@@ -403,8 +401,7 @@ def augment_scenes(coordinates: Sequence[torch.Tensor], colors: Sequence[torch.T
     else:
         xyz_out, feat_out = out
         for t, w in ((xyz_out, 3), (feat_out, 6)):
-            if not t.is_cuda:
-                raise L.Pq3dError("pq3d_amd kernels need device tensors (no CPU fallback)")
+            _need_device(t)
             if t.dtype != torch.float32 or tuple(t.shape) != (P, w) or not t.is_contiguous() or t.device != dev:
                 raise ValueError(f"augment_scenes: out must be contiguous fp32 tensors [{P}, 3] and [{P}, 6] on {dev}")
     offp = C.cast(off, C.c_void_p)

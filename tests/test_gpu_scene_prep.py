@@ -65,6 +65,32 @@ def test_voxelize_ragged_batch_with_a_one_point_scene():
     _check_voxelize([c, c])
 
 
+@pytest.mark.parametrize("P", [2047, 2048, 2049])
+def test_voxelize_around_one_scan_block(P):
+    """One block of the count / emit kernels' scan is PQ3D_VOXELIZE_BLOCK = 2048 points."""
+    r = np.random.default_rng(P)
+    _check_voxelize([r.uniform(-0.4, 0.4, (P, 3)).astype(np.float32)])
+
+
+def test_voxelize_eight_scenes_with_boundaries_inside_a_block():
+    """The scene table's maximum: one-point scenes, boundaries inside a 2048-point block (rows 1, 701, 702, 2049, 4098,
+    4101) and one on a block's first row (2048)."""
+    r = np.random.default_rng(14)
+    lens = [1, 700, 1, 1346, 1, 2049, 3, 500]
+    assert np.cumsum(lens).tolist()[:5] == [1, 701, 702, 2048, 2049]
+    _check_voxelize([r.uniform(-0.3, 0.3, (n, 3)).astype(np.float32) for n in lens])
+
+
+def test_voxelize_more_block_sums_than_scan_threads():
+    """Above 2048 * 1024 points every thread of the one-workgroup scan of the block sums takes more than one of them.  The
+    points come from 300 voxels, so that the restatement's table stays small."""
+    r = np.random.default_rng(15)
+    P = 2048 * 1024 + 3
+    centres = (r.integers(-40, 40, (300, 3)) + 0.5) * VS
+    pts = (centres[r.integers(0, 300, P)] + r.uniform(-0.4, 0.4, (P, 3)) * VS).astype(np.float32)
+    _check_voxelize([pts])
+
+
 def test_voxelize_many_duplicates():
     """5000 points in about 40 voxels: long runs on one table slot, atomicMin contention on the representative."""
     r = np.random.default_rng(8)
@@ -181,6 +207,17 @@ def test_fps_ragged_batch_equals_single_calls():
     got = _check_fps(clouds, 50, start_idx=7)
     for b, c in enumerate(clouds):
         assert np.array_equal(scene.farthest_point_sample([_dev(c)], 50, 7).cpu().numpy()[0], got[b])
+
+
+def test_fps_sixty_four_small_scenes():
+    """The scene table's maximum, PQ3D_FPS_MAX_SCENES = 64: scenes of 1 to 70 points at m = 1, which is also the smallest
+    scene; then 64 scenes of 5 to 70 points at m = 5, their smallest."""
+    r = np.random.default_rng(16)
+    lens = (1 + np.arange(64) * 37 % 70).tolist()
+    assert len(lens) == 64 and min(lens) == 1 and max(lens) == 70
+    _check_fps([r.uniform(-2, 2, (n, 3)).astype(np.float32) for n in lens], 1)
+    lens = [max(n, 5) for n in lens]
+    _check_fps([r.uniform(-2, 2, (n, 3)).astype(np.float32) for n in lens], 5, start_idx=4)
 
 
 @functools.lru_cache(maxsize=None)

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(CT) void chain_ca_fwd_kernel(const pq3d_chain_ca_de
         load4<true>(d.op[m], base, ov);
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = xr[k] + ov[k];
-        const RowStats st = row_stats4(v, d.eps);
+        const RowStats st = ln_row_stats(v, D, d.eps, AllCols{});
         const float w = d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)M;
         load4<false>(d.gamma[m], c.lane * 4, gm);
         load4<false>(d.beta[m], c.lane * 4, bt);

@@ -5,7 +5,8 @@
 #pragma once
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_common.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -139,19 +140,7 @@ PQ_DEV void handoff(const Ctx& c, unsigned* mine, unsigned* group, unsigned targ
   __syncthreads();
 }
 
-// ---- LayerNorm rows (norm.hip's add_ln_fwd at d = 256: lane owns columns 4 lane .. 4 lane + 3)
-struct RowStats { float mean, rstd; };
-PQ_DEV RowStats row_stats4(const float (&v)[4], float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s += v[j];
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { const float t = v[j] - mean; q += t * t; }
-  const float var = wave_sum(q) / (float)D;
-  return {mean, 1.f / sqrtf(var + eps)};
-}
+// ---- LayerNorm rows (ln_row.h's arithmetic, shared with norm.hip, at d = 256: lane owns columns 4 lane .. 4 lane + 3)
 // y = LN(x + (o_0 + ... + o_{nsum-1})); the sum is kept in osum when given
 template <bool SC1X>
 PQ_DEV void ln_row(const Ctx& c, long row, const float* x, const float* const* o, int nsum, long ostride, const float* gamma,
@@ -169,7 +158,7 @@ PQ_DEV void ln_row(const Ctx& c, long row, const float* x, const float* const* o
   if (osum) *(float4*)(osum + base) = make_float4(ov[0], ov[1], ov[2], ov[3]);
 #pragma unroll
   for (int j = 0; j < 4; ++j) v[j] = xr[j] + ov[j];
-  const RowStats st = row_stats4(v, eps);
+  const RowStats st = ln_row_stats(v, D, eps, AllCols{});
   load4<false>(gamma, c.lane * 4, gm);
   load4<false>(beta, c.lane * 4, bt);
 #pragma unroll
@@ -333,15 +322,6 @@ PQ_DEV void tproj_issue_w(const Ctx& c, int j, int ng, const float* const* W, Ra
       load8<false>(W[g], (long)(l * TPK + (ch >> 4)) * D + n0 + (ch & 15) * 8, wb[l].v[i]);
     }
 }
-PQ_DEV u32x4 tp_km_frag(const bf16_t* tile, int ldk, int r0, int ks, int li, int lg) {   // gemm_common.h's km_frag
-  typedef short v4s_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-  const bf16_t* p0 = tile + (ks * 32 + 8 * lg + (li >> 2)) * ldk + r0 + 4 * (li & 3);
-  const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)p0);
-  const v4s_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(p0 + 4 * ldk));
-  const u32x2 lo = __builtin_bit_cast(u32x2, a), hi = __builtin_bit_cast(u32x2, b);
-  return (u32x4){lo.x, lo.y, hi.x, hi.y};
-}
 template <int NRT, bool SC1A, typename TO>
 PQ_DEV void tproj_3x256(const Ctx& c, unsigned char* smem, int j, int ng, int m0, int R, const float* const* A, const float* const* aux,
                         TO* const* out, RawB (&wb)[2]) {
@@ -377,7 +357,7 @@ PQ_DEV void tproj_3x256(const Ctx& c, unsigned char* smem, int j, int ng, int m0
     for (int ks = 0; ks < TPK / 32; ++ks) {
       u32x4 bh[2];
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb) bh[nb] = tp_km_frag(Bp, TPLD, wc + nb * 16, ks, c.li, c.lg);
+      for (int nb = 0; nb < 2; ++nb) bh[nb] = km_frag(Bp, TPLD, wc + nb * 16, ks, c.li, c.lg);
 #pragma unroll
       for (int t = 0; t < NRT; ++t) {
         const u32x4 ah = *(const u32x4*)&Ap[t * TM * LDR + (wr + c.li) * LDR + l * TPK + ks * 32 + c.lg * 8];

@@ -13,7 +13,6 @@
 #include <atomic>
 
 #include "chain_common.h"
-#include "gemm_common.h"
 
 namespace {
 
@@ -33,27 +32,6 @@ constexpr size_t bwd_lds(int nrt) {
   return m > sl ? m : sl;
 }
 
-// one LayerNorm backward row (norm.hip's add_ln_bwd at M = 1, no dropout): returns g = d(x + o); accumulates this lane's
-// parameter-gradient partials.  dyin: upstream gradient row (4 values of this lane)
-PQ_DEV void ln_bwd_row(const float (&v)[4], const float (&dyr)[4], const float (&gam)[4], float mean, float rstd, float (&g)[4],
-                       float (&dg)[4], float (&db)[4]) {
-  float xh[4], dz[4];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float du = 1.f * dyr[j];
-    xh[j] = (v[j] - mean) * rstd;
-    dg[j] += du * xh[j];
-    db[j] += du;
-    dz[j] = du * gam[j];
-    s1 += dz[j];
-    s2 += dz[j] * xh[j];
-  }
-  s1 = wave_sum(s1) / (float)D;
-  s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) g[j] = rstd * (dz[j] - s1 - xh[j] * s2);
-}
 template <int NRT>
 __global__ __launch_bounds__(CT) void chain_ffn_bwd_kernel(const pq3d_chain_ffn_bwd_desc d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ch_smem[];
@@ -162,7 +140,7 @@ __global__ __launch_bounds__(CT) void chain_ffn_bwd_kernel(const pq3d_chain_ffn_
       load4<false>(d.g2, c.lane * 4, gam);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = xv[k] + ov[k];
-      ln_bwd_row(v, dyr, gam, d.mean2[lrow], d.rstd2[lrow], g, dg, db);
+      ln_bwd_row(v, dyr, gam, 1.f, d.mean2[lrow], d.rstd2[lrow], D, AllCols{}, g, dg, db);   // ln_row.h: add_ln_bwd at M = 1, no dropout
       *(float4*)(d.dy + lbase) = make_float4(g[0], g[1], g[2], g[3]);
     }
     ln_partials_store(c, (float*)ch_smem, dg, db, lnws + j * 1024);
@@ -324,7 +302,7 @@ __global__ __launch_bounds__(CT) void chain_ffn_bwd_kernel(const pq3d_chain_ffn_
       load4<false>(d.g1, c.lane * 4, gam);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = xv[k] + ov[k];
-      ln_bwd_row(v, dyr, gam, d.mean1[lrow], d.rstd1[lrow], g, dg, db);
+      ln_bwd_row(v, dyr, gam, 1.f, d.mean1[lrow], d.rstd1[lrow], D, AllCols{}, g, dg, db);
       *(float4*)(d.df + lbase) = make_float4(g[0], g[1], g[2], g[3]);
     }
     ln_partials_store(c, (float*)ch_smem, dg, db, lnws + j * 1024 + 512);

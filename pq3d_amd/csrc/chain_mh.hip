@@ -12,7 +12,6 @@
 #include <atomic>
 
 #include "chain_common.h"
-#include "gemm_common.h"
 
 namespace {
 
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(CT) void chain_mh_fwd_kernel(const pq3d_chain_mh_de
       load4<true>(d.h1, base, ov);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = 0.f + ov[k];
-      const RowStats st = row_stats4(v, d.eps);
+      const RowStats st = ln_row_stats(v, D, d.eps, AllCols{});
       load4<false>(d.gamma, c.lane * 4, gm);
       load4<false>(d.beta, c.lane * 4, bt);
 #pragma unroll
@@ -178,26 +177,6 @@ template <int NRT> constexpr size_t mhb_lds() {
   const size_t s = (size_t)NRT * TM * LDR * 2 + (size_t)D * S0LD * 2 + (size_t)TM * 36 * 4;
   const size_t sl = (size_t)2 * 8 * D * 4;
   return s > sl ? s : sl;
-}
-
-PQ_DEV void ln_bwd_row(const float (&v)[4], const float (&dyr)[4], const float (&gam)[4], float mean, float rstd, float (&g)[4],
-                       float (&dg)[4], float (&db)[4]) {   // norm.hip's add_ln_bwd at M = 1, no dropout
-  float xh[4], dz[4];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float du = 1.f * dyr[j];
-    xh[j] = (v[j] - mean) * rstd;
-    dg[j] += du * xh[j];
-    db[j] += du;
-    dz[j] = du * gam[j];
-    s1 += dz[j];
-    s2 += dz[j] * xh[j];
-  }
-  s1 = wave_sum(s1) / (float)D;
-  s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) g[j] = rstd * (dz[j] - s1 - xh[j] * s2);
 }
 
 template <int NRT>
@@ -309,7 +288,7 @@ __global__ __launch_bounds__(CT) void chain_mh_bwd_kernel(const pq3d_chain_mh_bw
       load4<false>(d.gamma, c.lane * 4, gam);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = 0.f + ov[k];
-      ln_bwd_row(v, dyr, gam, d.mean[lrow], d.rstd[lrow], g, dg, db);
+      ln_bwd_row(v, dyr, gam, 1.f, d.mean[lrow], d.rstd[lrow], D, AllCols{}, g, dg, db);   // ln_row.h: add_ln_bwd at M = 1, no dropout
       *(u32x2*)((bf16_t*)d.dpre + lbase) = (u32x2){pack_bf2(ov[0] > 0.f ? g[0] : 0.f, ov[1] > 0.f ? g[1] : 0.f),
                                                    pack_bf2(ov[2] > 0.f ? g[2] : 0.f, ov[3] > 0.f ? g[3] : 0.f)};
     }

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(CT) void chain_sa_bwd_kernel(const pq3d_chain_sa_bw
     tproj_3x256<NRT, false, float>(c, ch_smem, j, 3, m0, R, d.dqkv, aux, d.g3, w1);
   }
   handoff(c, mine, group, v0 + 1, d.err);
-  // ---- 2. merged LayerNorm backward over the M branches (norm.hip's add_ln_bwd_merged, no dropout)
+  // ---- 2. merged LayerNorm backward over the M branches (ln_row.h: add_ln_bwd_merged's row, no dropout)
   {
     const long row = m0 + 4 * NRT * j + c.wave;
     const bool on = c.wave < 4 * NRT && row < R;
@@ -51,43 +51,23 @@ __global__ __launch_bounds__(CT) void chain_sa_bwd_kernel(const pq3d_chain_sa_bw
 #pragma unroll
       for (int k = 0; k < 4; ++k) { dg[m][k] = 0.f; db[m][k] = 0.f; }
     if (on) {
-      float xv[4], dyr[4], gsum[4] = {0.f, 0.f, 0.f, 0.f}, t[4];
+      float xv[4], dyr[4], gsum[4] = {0.f, 0.f, 0.f, 0.f};
       load4<false>(d.x, base, xv);
-      load4<true>(d.g3[0], base, dyr);
-      load4<true>(d.g3[1], base, t);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dyr[k] += t[k];
-      load4<true>(d.g3[2], base, t);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dyr[k] += t[k];
+      add3_rows([&](int i, float (&t)[4]) { load4<true>(d.g3[i], base, t); }, true, true, dyr);
 #pragma unroll
       for (int m = 0; m < 3; ++m) {
         if (m < M) {
-          float ov[4], gam[4], xh[4], dz[4], go[4];
+          float ov[4], gam[4], v[4], g[4];
           load4<false>(d.op[m], base, ov);
           load4<false>(d.gamma[m], c.lane * 4, gam);
           const float mean = d.mean[(long)m * R + row], rstd = d.rstd[(long)m * R + row];
           const float w = d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)M;
-          float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float du = w * dyr[k];
-            xh[k] = ((xv[k] + ov[k]) - mean) * rstd;
-            dg[m][k] += du * xh[k];
-            db[m][k] += du;
-            dz[k] = du * gam[k];
-            s1 += dz[k];
-            s2 += dz[k] * xh[k];
-          }
-          s1 = wave_sum(s1) / (float)D;
-          s2 = wave_sum(s2) / (float)D;
+          for (int k = 0; k < 4; ++k) v[k] = xv[k] + ov[k];
+          ln_bwd_row(v, dyr, gam, w, mean, rstd, D, AllCols{}, g, dg[m], db[m]);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float g = rstd * (dz[k] - s1 - xh[k] * s2);
-            gsum[k] += g;
-            go[k] = g;
-          }
-          *(float4*)(d.dop[m] + base) = make_float4(go[0], go[1], go[2], go[3]);
+          for (int k = 0; k < 4; ++k) gsum[k] += g[k];
+          *(float4*)(d.dop[m] + base) = make_float4(g[0], g[1], g[2], g[3]);
         }
       }
       *(float4*)(d.dxr + base) = make_float4(gsum[0], gsum[1], gsum[2], gsum[3]);

@@ -10,14 +10,12 @@
 // Large R: waves walk rows with a grid stride and keep the NEXT row's loads in flight.
 #include <cstdlib>
 
-#include "common.h"
+#include "ln_row.h"
 
 namespace {
 
 constexpr int MAXPL = 32;  // values per lane -> d <= 2048 (round 4: 1152-wide MLP heads of a 768-wide decoder ran into 1024)
 constexpr int WPB = 4;     // waves (rows in flight) per block
-
-struct RowStats { float mean, rstd; };
 
 template <int PL, bool VEC> PQ_DEV int colof(int lane, int j) { return VEC ? (j >> 2) * 256 + lane * 4 + (j & 3) : lane + 64 * j; }
 
@@ -68,20 +66,37 @@ PQ_DEV void store_row(void* p, int dt, long base, int lane, int d, const float (
   }
 }
 
+// the upstream gradient row: dy, or (dy + dy2) + dy3
 template <int PL, bool VEC>
-PQ_DEV RowStats row_stats(const float (&v)[PL], int d, int lane, float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < PL; ++j) s += (colof<PL, VEC>(lane, j) < d) ? v[j] : 0.f;
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
+PQ_DEV void load_dy_row(const pq3d_ln_desc& d, const float* dy, long base, int lane, float (&dyr)[PL]) {
+  add3_rows([&](int i, float (&t)[PL]) { load_row<PL, VEC>(i == 0 ? dy : (i == 1 ? d.dy2 : d.dy3), PQ3D_F32, base, lane, d.d, t); },
+            d.dy2 != nullptr, d.dy3 != nullptr, dyr);
+}
+
+// Block-level reduction of parameter-gradient partials: NA arrays of per-lane column sums go from registers to LDS
+// [array][wave][column], then ONE atomic per column per block and array
+template <int PL, bool VEC, int NW, int NA>
+PQ_DEV void ln_param_grads_flush(float (&red)[NA][NW][64 * PL], const float* const (&acc)[NA], float* const (&out)[NA], int d) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < PL; ++j) {
-    const float t = v[j] - mean;
-    q += (colof<PL, VEC>(lane, j) < d) ? t * t : 0.f;
+    const int c = colof<PL, VEC>(lane, j);
+#pragma unroll
+    for (int a = 0; a < NA; ++a) red[a][wave][c] = acc[a][j];
   }
-  const float var = wave_sum(q) / (float)d;
-  return {mean, 1.f / sqrtf(var + eps)};
+  __syncthreads();
+  for (int c = threadIdx.x; c < d; c += NW * 64) {
+    float sum[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) sum[a] = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+#pragma unroll
+      for (int a = 0; a < NA; ++a) sum[a] += red[a][w][c];
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) unsafeAtomicAdd(&out[a][c], sum[a]);
+  }
 }
 
 template <int PL, bool VEC>
@@ -134,15 +149,11 @@ __global__ __launch_bounds__(WPB * 64) void add_ln_fwd_kernel(const pq3d_ln_desc
         }
         if (d.osum) store_row<PL, VEC>(d.osum, PQ3D_F32, base, lane, d.d, ov);   // kept for the backward pass
       }
-      if (drop) {   // uniform branch around pure ALU: residual dropout of branch m (site drop.site + m)
-        const DropState ds = drop_init(d.drop, m, d.d);
-#pragma unroll
-        for (int j = 0; j < PL; ++j)
-          ov[j] = drop_keep(ds, (uint32_t)row, (uint32_t)colof<PL, VEC>(lane, j)) ? ov[j] * ds.scale : 0.f;
-      }
+      // uniform branch around pure ALU: residual dropout of branch m (site drop.site + m)
+      if (drop) res_dropout_row(ov, drop_init(d.drop, m, d.d), row, [&](int j) { return colof<PL, VEC>(lane, j); });
 #pragma unroll
       for (int j = 0; j < PL; ++j) v[j] = (colof<PL, VEC>(lane, j) < d.d) ? xr[j] + ov[j] : 0.f;
-      const RowStats st = row_stats<PL, VEC>(v, d.d, lane, d.eps);
+      const RowStats st = ln_row_stats(v, d.d, d.eps, [&](int j) { return colof<PL, VEC>(lane, j) < d.d; });
       const float w = (d.independent || d.sum_branches) ? 1.f
                       : (d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)d.M);
       float gm[PL], bt[PL];
@@ -173,6 +184,8 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
 #endif
   __shared__ float red[2][NW][64 * PL];
   const int lane = threadIdx.x & 63;
+  const auto col = [&](int j) { return colof<PL, VEC>(lane, j); };
+  const auto valid = [&](int j) { return colof<PL, VEC>(lane, j) < d.d; };
   const int m = blockIdx.y;
   const long wave_id = (long)blockIdx.x * NW + (threadIdx.x >> 6), nwaves = (long)gridDim.x * NW;
   const long nscene = d.coef ? d.R / d.rows_per_scene : 1;
@@ -196,18 +209,7 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
       for (int j = 0; j < PL; ++j) xv[j] = 0.f;
     }
     load_row<PL, VEC>(d.o[m], d.dt_o, base, lane, d.d, ov);
-    load_row<PL, VEC>(dyp, PQ3D_F32, base, lane, d.d, ndy);
-    if (d.dy2) {   // upstream gradient in up to three addends: (dy + dy2) + dy3
-      float t[PL];
-      load_row<PL, VEC>(d.dy2, PQ3D_F32, base, lane, d.d, t);
-#pragma unroll
-      for (int j = 0; j < PL; ++j) ndy[j] += t[j];
-      if (d.dy3) {
-        load_row<PL, VEC>(d.dy3, PQ3D_F32, base, lane, d.d, t);
-#pragma unroll
-        for (int j = 0; j < PL; ++j) ndy[j] += t[j];
-      }
-    }
+    load_dy_row<PL, VEC>(d, dyp, base, lane, ndy);
     if (d.sum_branches) {
       for (int p = 1; p < d.M; ++p) {
         float t[PL];
@@ -216,15 +218,7 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
         for (int j = 0; j < PL; ++j) ov[j] += t[j];
       }
     }
-    if (drop) {
-      nkeep = 0;
-#pragma unroll
-      for (int j = 0; j < PL; ++j) {
-        const bool k = drop_keep(dst, (uint32_t)row, (uint32_t)colof<PL, VEC>(lane, j));
-        nkeep |= (unsigned)k << j;
-        ov[j] = k ? ov[j] * dst.scale : 0.f;
-      }
-    }
+    if (drop) nkeep = res_dropout_row(ov, dst, row, col);
 #pragma unroll
     for (int j = 0; j < PL; ++j) nv[j] = xv[j] + ov[j];
   };
@@ -239,28 +233,10 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
     const float w = (d.independent || d.sum_branches) ? 1.f
                     : (d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)d.M);
     if (row + nwaves < d.R) fetch(row + nwaves);
-    float xh[PL], dz[PL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < PL; ++j) {
-      if (colof<PL, VEC>(lane, j) < d.d) {
-        const float du = w * dyr[j];
-        xh[j] = (v[j] - mean) * rstd;
-        dg[j] += du * xh[j];
-        db[j] += du;
-        dz[j] = du * gam[j];
-        s1 += dz[j];
-        s2 += dz[j] * xh[j];
-      } else { xh[j] = 0.f; dz[j] = 0.f; }
-    }
-    s1 = wave_sum(s1) / (float)d.d;
-    s2 = wave_sum(s2) / (float)d.d;
     float g[PL], go[PL];
+    ln_bwd_row(v, dyr, gam, w, mean, rstd, d.d, valid, g, dg, db);
 #pragma unroll
-    for (int j = 0; j < PL; ++j) {
-      g[j] = rstd * (dz[j] - s1 - xh[j] * s2);
-      go[j] = drop ? (((keep >> j) & 1u) ? g[j] * dst.scale : 0.f) : g[j];
-    }
+    for (int j = 0; j < PL; ++j) go[j] = drop ? (((keep >> j) & 1u) ? g[j] * dst.scale : 0.f) : g[j];
     store_row<PL, VEC>(d.d_o[m], PQ3D_F32, base, lane, d.d, go);
     if (d.dx && !d.independent) {
       if (d.M == 1 || d.sum_branches) store_row<PL, VEC>(d.dx, PQ3D_F32, base, lane, d.d, g);
@@ -273,22 +249,7 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
       }
     }
   }
-  // block-level reduction of the parameter-gradient partials (LDS index = column)
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < PL; ++j) {
-    const int c = colof<PL, VEC>(lane, j);
-    red[0][wave][c] = dg[j];
-    red[1][wave][c] = db[j];
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < d.d; c += NW * 64) {   // ONE atomic per column per block
-    float sg = 0.f, sb = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) { sg += red[0][w][c]; sb += red[1][w][c]; }
-    unsafeAtomicAdd(&d.dgamma[m][c], sg);
-    unsafeAtomicAdd(&d.dbeta[m][c], sb);
-  }
+  ln_param_grads_flush<PL, VEC, NW>(red, {dg, db}, {d.dgamma[m], d.dbeta[m]}, d.d);
 }
 
 // Merged-branch backward for the big streaming calls (the cross-attention sublayer of a large batch: M = 3 memories, R in the
@@ -300,6 +261,8 @@ template <int PL, bool VEC, int NW, int MB>
 __global__ __launch_bounds__(NW * 64) void add_ln_bwd_merged_kernel(const pq3d_ln_desc d) {
   __shared__ float red[2][NW][64 * PL];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const auto col = [&](int j) { return colof<PL, VEC>(lane, j); };
+  const auto valid = [&](int j) { return colof<PL, VEC>(lane, j) < d.d; };
   const long wave_id = (long)blockIdx.x * NW + wave, nwaves = (long)gridDim.x * NW;
   const long nscene = d.coef ? d.R / d.rows_per_scene : 1;
   float dg[MB][PL], db[MB][PL];   // (gamma is re-read per row: L1-resident, and 2 MB PL accumulators already fill the budget)
@@ -317,18 +280,7 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_merged_kernel(const pq3d_l
 #pragma unroll
       for (int j = 0; j < PL; ++j) xv[j] = 0.f;
     }
-    load_row<PL, VEC>(d.dy, PQ3D_F32, base, lane, d.d, dyr);
-    if (d.dy2) {   // upstream gradient in up to three addends: (dy + dy2) + dy3
-      float t[PL];
-      load_row<PL, VEC>(d.dy2, PQ3D_F32, base, lane, d.d, t);
-#pragma unroll
-      for (int j = 0; j < PL; ++j) dyr[j] += t[j];
-      if (d.dy3) {
-        load_row<PL, VEC>(d.dy3, PQ3D_F32, base, lane, d.d, t);
-#pragma unroll
-        for (int j = 0; j < PL; ++j) dyr[j] += t[j];
-      }
-    }
+    load_dy_row<PL, VEC>(d, d.dy, base, lane, dyr);
 #pragma unroll
     for (int j = 0; j < PL; ++j) gsum[j] = 0.f;
 #pragma unroll
@@ -340,60 +292,27 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_merged_kernel(const pq3d_l
       DropState dst;
       if (drop) {
         dst = drop_init(d.drop, m, d.d);
-        keep = 0;
-#pragma unroll
-        for (int j = 0; j < PL; ++j) {
-          const bool k = drop_keep(dst, (uint32_t)row, (uint32_t)colof<PL, VEC>(lane, j));
-          keep |= (unsigned)k << j;
-          ov[j] = k ? ov[j] * dst.scale : 0.f;
-        }
+        keep = res_dropout_row(ov, dst, row, col);
       }
       const float mean = d.mean[(long)m * d.R + row], rstd = d.rstd[(long)m * d.R + row];
       const float w = d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)d.M;
-      float xh[PL], dz[PL];
-      float s1 = 0.f, s2 = 0.f;
+      float v[PL], g[PL], go[PL];
+#pragma unroll
+      for (int j = 0; j < PL; ++j) v[j] = xv[j] + ov[j];
+      ln_bwd_row(v, dyr, gam, w, mean, rstd, d.d, valid, g, dg[m], db[m]);
 #pragma unroll
       for (int j = 0; j < PL; ++j) {
-        if (colof<PL, VEC>(lane, j) < d.d) {
-          const float du = w * dyr[j];
-          xh[j] = ((xv[j] + ov[j]) - mean) * rstd;
-          dg[m][j] += du * xh[j];
-          db[m][j] += du;
-          dz[j] = du * gam[j];
-          s1 += dz[j];
-          s2 += dz[j] * xh[j];
-        } else { xh[j] = 0.f; dz[j] = 0.f; }
-      }
-      s1 = wave_sum(s1) / (float)d.d;
-      s2 = wave_sum(s2) / (float)d.d;
-      float go[PL];
-#pragma unroll
-      for (int j = 0; j < PL; ++j) {
-        const float g = rstd * (dz[j] - s1 - xh[j] * s2);
-        gsum[j] += g;
-        go[j] = drop ? (((keep >> j) & 1u) ? g * dst.scale : 0.f) : g;
+        gsum[j] += g[j];
+        go[j] = drop ? (((keep >> j) & 1u) ? g[j] * dst.scale : 0.f) : g[j];
       }
       store_row<PL, VEC>(d.d_o[m], PQ3D_F32, base, lane, d.d, go);
     }
     store_row<PL, VEC>(d.dx, PQ3D_F32, base, lane, d.d, gsum);
   }
-  // block-level reduction of the parameter-gradient partials, one branch after the other (LDS index = column)
+  // the parameter-gradient partials, one branch after the other through the same LDS
 #pragma unroll
   for (int m = 0; m < MB; ++m) {
-#pragma unroll
-    for (int j = 0; j < PL; ++j) {
-      const int c = colof<PL, VEC>(lane, j);
-      red[0][wave][c] = dg[m][j];
-      red[1][wave][c] = db[m][j];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < d.d; c += NW * 64) {   // ONE atomic per column per block
-      float sg = 0.f, sb = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { sg += red[0][w][c]; sb += red[1][w][c]; }
-      unsafeAtomicAdd(&d.dgamma[m][c], sg);
-      unsafeAtomicAdd(&d.dbeta[m][c], sb);
-    }
+    ln_param_grads_flush<PL, VEC, NW>(red, {dg[m], db[m]}, {d.dgamma[m], d.dbeta[m]}, d.d);
     __syncthreads();
   }
 }
@@ -448,6 +367,13 @@ bool ln_vec_ok(const pq3d_ln_desc& d, bool bwd, bool no_dx_atomics = false) {
   else if (d.d == 768 && vec) { LAUNCH(12, true); }                                     \
   else if (d.d <= 1024) { if (vec) { LAUNCH(16, true); } else { LAUNCH(16, false); } } \
   else { if (vec) { LAUNCH(32, true); } else { LAUNCH(32, false); } }
+
+// The merged backward exists up to PL = 12: wider rows would spill its 6 PL accumulators, and pq3d_add_ln_bwd never selects it
+// for them.  8 waves per block also for the query-sized calls (one row per wave at R = 800): measured at config 2, same box, 4
+// waves x 2 rows 1.4155 ms per step (= the atomics kernel), 8 waves 1.409
+template <int PL, bool VEC> void launch_bwd_merged(dim3 grid, hipStream_t s, const pq3d_ln_desc& d) {
+  if constexpr (PL <= 12) hipLaunchKernelGGL((add_ln_bwd_merged_kernel<PL, VEC, 8, 3>), grid, dim3(512), 0, s, d);
+}
 
 }  // namespace
 
@@ -512,14 +438,8 @@ extern "C" int pq3d_add_ln_bwd(const pq3d_ln_desc* dp, void* stream) {
   if (merged) {
     grid.y = 1;
     const bool vecm = ln_vec_ok(d, true, true);
-    // 8 waves per block also for the query-sized calls (one row per wave at R = 800): measured at config 2, same box, 4
-    // waves x 2 rows 1.4155 ms per step (= the atomics kernel), 8 waves 1.409
-#define BWDM(PLV, V) hipLaunchKernelGGL((add_ln_bwd_merged_kernel<PLV, V, 8, 3>), grid, dim3(512), 0, s, d)
-    if (d.d <= 64) { BWDM(1, false); }
-    else if (d.d <= 128) { BWDM(2, false); }
-    else if (d.d <= 256) { if (vecm) { BWDM(4, true); } else { BWDM(4, false); } }
-    else if (d.d <= 512) { if (vecm) { BWDM(8, true); } else { BWDM(8, false); } }
-    else { BWDM(12, true); }
+#define BWDM(PLV, V) launch_bwd_merged<PLV, V>(grid, s, d)
+    LN_DISPATCH(BWDM, vecm)
 #undef BWDM
     PQ_LAUNCH_CHECK();
     return 0;
@@ -567,7 +487,7 @@ __global__ __launch_bounds__(WPB * 64) void rmsnorm_bwd_kernel(const float* __re
                                                                float* __restrict__ dx, float* __restrict__ dw, long R, int d,
                                                                const float* __restrict__ dres, const pq3d_dropout dr,
                                                                float* __restrict__ dxm) {
-  __shared__ float red[WPB][64 * PL];
+  __shared__ float red[1][WPB][64 * PL];
   // dxm (optional): a second copy of dx with the dropout mask (x 1/(1-p)) of site `dr` over [R, d] applied -- the gradient
   // the PRECEDING sublayer's output projection needs (x = residual + dropout(o W^T): its dropout's backward), written here
   // instead of by a launch of its own
@@ -601,18 +521,11 @@ __global__ __launch_bounds__(WPB * 64) void rmsnorm_bwd_kernel(const float* __re
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < PL; ++j) red[wave][lane + 64 * j] = acc[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < d; c += WPB * 64) {
-    float sres = 0.f;
-#pragma unroll
-    for (int wv_ = 0; wv_ < WPB; ++wv_) sres += red[wv_][c];
-    unsafeAtomicAdd(&dw[c], sres);
-  }
+  ln_param_grads_flush<PL, false, WPB>(red, {acc}, {dw}, d);
 }
 }  // namespace
 
+// (not LN_DISPATCH: its 768-wide rung would instantiate a PL = 12 pair of these kernels that no call can reach)
 #define RMS_DISPATCH(kernel, grid, ...)                                                                  \
   if (d <= 64) hipLaunchKernelGGL((kernel<1>), grid, dim3(WPB * 64), 0, s, __VA_ARGS__);                \
   else if (d <= 128) hipLaunchKernelGGL((kernel<2>), grid, dim3(WPB * 64), 0, s, __VA_ARGS__);          \

@@ -31,6 +31,7 @@ from torch.autograd import Function
 from . import _lib as L
 from . import arena, attn, ops, wgrad
 from .attn import sa_fold_ok
+from .ops import ln_bwd as _ln_bwd, ln_fwd as _ln_fwd   # (tests reach them as fused._ln_fwd / fused._ln_bwd)
 from .wgrad import _colsum_acc  # noqa: F401  (importable from fused as before: tests/test_gpu_ops.py)
 from ._lib import BF16
 
@@ -164,46 +165,6 @@ def _mh_forward(spec, x, keys, inv_den, seg_pad, rec, call):
            row_fill_flag=seg_pad, row_fill=-1e6, mask_out=amask)
     rec.update(mh_x=x.detach(), mh_h1=h1, mh_h2=h2, mh_mean=mean, mh_rstd=rstd, mh_qm=qm, mh_drop=hdrop)
     return cls, mlog, amask
-
-
-def _ln_fwd(x, os_, gammas, betas, eps, coef, rows_per_scene, out_dtype=torch.float32, drop=None, sum_branches=False,
-            osum=None):
-    M = len(os_)
-    dm = os_[0].shape[-1]
-    R = os_[0].numel() // dm
-    y = torch.empty(os_[0].shape, dtype=out_dtype, device=os_[0].device)
-    mean = torch.empty(M, R, dtype=torch.float32, device=y.device)
-    rstd = torch.empty_like(mean)
-    d = ops._ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, drop)
-    d.sum_branches, d.osum = int(sum_branches), L.ptr(osum)
-    nb = (M + 1 + (x is not None)) * R * dm * 4.0
-    L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
-    return y, mean, rstd
-
-
-def _ln_bwd(x, os_, gammas, betas, eps, coef, rows_per_scene, mean, rstd, dy, dgs, dbs, want_dx=True, dup_dx=False,
-            drop=None, sum_branches=False, dx_zeroed=None):
-    """Returns (dx or None, d_o [M,...] fp32 stacked); dgamma/dbeta accumulate into the arena views dgs/dbs.
-    dup_dx: also write the (single-branch) input gradient to a second buffer even without a residual input."""
-    M = len(os_)
-    dm = os_[0].shape[-1]
-    R = os_[0].numel() // dm
-    dys = list(dy) if isinstance(dy, (list, tuple)) else [dy]   # up to three addends of the upstream gradient, summed in the kernel
-    dy = dys[0]
-    dev = dy.device
-    d_o = torch.empty(1 if sum_branches else M, *os_[0].shape, dtype=torch.float32, device=dev)
-    dx = torch.empty(os_[0].shape, dtype=torch.float32, device=dev) if ((x is not None and want_dx) or dup_dx) else None
-    d = ops._ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, None, mean, rstd, drop)
-    if dx_zeroed is not None and dx is not None:   # a slice of the caller's buffer zeroed once for the whole backward
-        dx, d.dx_zeroed = dx_zeroed, 1
-    d.dy, d.dx, d.accumulate, d.sum_branches = L.ptr(dy), L.ptr(dx), 1, int(sum_branches)
-    if len(dys) > 1:
-        d.dy2, d.dy3 = L.ptr(dys[1]), L.ptr(dys[2]) if len(dys) > 2 else None
-    for m in range(1 if sum_branches else M):
-        d.d_o[m], d.dgamma[m], d.dbeta[m] = L.ptr(d_o[m]), L.ptr(dgs[m]), L.ptr(dbs[m])
-    nb = (3 * M + 1 + (x is not None)) * R * dm * 4.0
-    L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
-    return dx, d_o
 
 
 def _attn(q, k, v, o, lse, H, ct, zero_attn, bwd=None, **kw):

@@ -611,6 +611,48 @@ def _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, dr
     return d
 
 
+def ln_fwd(x, os_, gammas, betas, eps, coef, rows_per_scene, out_dtype=torch.float32, drop=None, sum_branches=False,
+           osum=None):
+    """One pq3d_add_ln_fwd launch on contiguous tensors.  Returns (y, mean [M, R], rstd [M, R])."""
+    M = len(os_)
+    dm = os_[0].shape[-1]
+    R = os_[0].numel() // dm
+    y = _empty(os_[0].shape, dtype=out_dtype, device=os_[0].device)
+    mean = _empty(M, R, dtype=torch.float32, device=y.device)
+    rstd = torch.empty_like(mean)
+    d = _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, drop)
+    d.sum_branches, d.osum = int(sum_branches), L.ptr(osum)
+    nb = (M + 1 + (x is not None)) * R * dm * 4.0
+    L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
+    return y, mean, rstd
+
+
+def ln_bwd(x, os_, gammas, betas, eps, coef, rows_per_scene, mean, rstd, dy, dgs, dbs, want_dx=True, dup_dx=False,
+           drop=None, sum_branches=False, dx_zeroed=None, accumulate=True):
+    """One pq3d_add_ln_bwd launch.  Returns (dx or None, d_o [M,...] fp32 stacked); dgamma/dbeta are added to dgs/dbs (the
+    arena views of the fused pass) or, with accumulate=False, written to them.
+    dup_dx: also write the (single-branch) input gradient to a second buffer even without a residual input."""
+    M = len(os_)
+    dm = os_[0].shape[-1]
+    R = os_[0].numel() // dm
+    dys = list(dy) if isinstance(dy, (list, tuple)) else [dy]   # up to three addends of the upstream gradient, summed in the kernel
+    dy = dys[0]
+    dev = dy.device
+    d_o = _empty(1 if sum_branches else M, *os_[0].shape, dtype=torch.float32, device=dev)
+    dx = _empty(os_[0].shape, dtype=torch.float32, device=dev) if ((x is not None and want_dx) or dup_dx) else None
+    d = _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, None, mean, rstd, drop)
+    if dx_zeroed is not None and dx is not None:   # a slice of the caller's buffer zeroed once for the whole backward
+        dx, d.dx_zeroed = dx_zeroed, 1
+    d.dy, d.dx, d.accumulate, d.sum_branches = L.ptr(dy), L.ptr(dx), int(accumulate), int(sum_branches)
+    if len(dys) > 1:
+        d.dy2, d.dy3 = L.ptr(dys[1]), L.ptr(dys[2]) if len(dys) > 2 else None
+    for m in range(1 if sum_branches else M):
+        d.d_o[m], d.dgamma[m], d.dbeta[m] = L.ptr(d_o[m]), L.ptr(dgs[m]), L.ptr(dbs[m])
+    nb = (3 * M + 1 + (x is not None)) * R * dm * 4.0
+    L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
+    return dx, d_o
+
+
 class _AddLN(Function):
     @staticmethod
     def forward(ctx, x, coef, eps, rows_per_scene, out_dtype, M, drop, sum_branches, *t):
@@ -618,15 +660,7 @@ class _AddLN(Function):
         os_ = [_c(a) for a in t[:M]]
         gammas, betas = [_c(a) for a in t[M:M + G]], [_c(a) for a in t[M + G:M + 2 * G]]
         x, coef = _c(x), _c(coef)
-        dm = os_[0].shape[-1]
-        R = os_[0].numel() // dm
-        y = _empty(os_[0].shape, dtype=out_dtype, device=os_[0].device)
-        mean = _empty(M, R, dtype=torch.float32, device=y.device)
-        rstd = torch.empty_like(mean)
-        d = _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, y, mean, rstd, drop)
-        d.sum_branches = int(sum_branches)
-        nb = (M + 1 + (x is not None)) * R * dm * 4.0
-        L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
+        y, mean, rstd = ln_fwd(x, os_, gammas, betas, eps, coef, rows_per_scene, out_dtype, drop, sum_branches)
         ctx.save_for_backward(x, coef, mean, rstd, *os_, *gammas, *betas)
         ctx.cfg = (eps, rows_per_scene, M, G, bool(sum_branches))
         ctx.drop = drop
@@ -639,18 +673,11 @@ class _AddLN(Function):
         t = ctx.saved_tensors[4:]
         os_, gammas, betas = t[:M], t[M:M + G], t[M + G:M + 2 * G]
         dy = dy.contiguous().float()
-        dev = dy.device
-        dx = _empty(os_[0].shape, dtype=torch.float32, device=dev) if x is not None else None
-        d_os = [_empty(o.shape, dtype=torch.float32, device=dev) for o in os_[:G]]
         dgs = [torch.empty_like(g) for g in gammas]
         dbs = [torch.empty_like(b) for b in betas]
-        d = _ln_desc(x, os_, gammas, betas, coef, eps, rows_per_scene, None, mean, rstd, ctx.drop)
-        d.dy, d.dx, d.sum_branches = L.ptr(dy), L.ptr(dx), int(sum_branches)
-        for m in range(G):
-            d.d_o[m], d.dgamma[m], d.dbeta[m] = L.ptr(d_os[m]), L.ptr(dgs[m]), L.ptr(dbs[m])
-        R, dm = os_[0].numel() // os_[0].shape[-1], os_[0].shape[-1]
-        nb = (3 * M + 1 + (x is not None)) * R * dm * 4.0
-        L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{dm}M{M}", 0.0, nb))
+        dx, d_o = ln_bwd(x, os_, gammas, betas, eps, coef, rows_per_scene, mean, rstd, dy, dgs, dbs, drop=ctx.drop,
+                         sum_branches=sum_branches, accumulate=False)
+        d_os = list(d_o)
         if x is not None and x.dtype != torch.float32:
             dx = dx.to(x.dtype)
         if sum_branches:      # every partial sum receives the gradient of the sum

@@ -302,6 +302,64 @@ def test_add_layernorm_wide_rows_many_rows(d):
         assert err < 5e-5, (i, err)
 
 
+@pytest.mark.parametrize("naddends", [3, 2])
+@pytest.mark.parametrize("M,R,d", [(1, 7, 100), (1, 7, 256), (3, 512, 256)])   # 4-byte layout with tail columns; 16-byte layout; merged kernel
+def test_add_layernorm_backward_gradient_addends(M, R, d, naddends):
+    """pq3d_add_ln_bwd with the upstream gradient in three (two) addends, dy = [a, b, c]: the kernel forms (a + b) + c per row, so
+    dx and d_o equal the call with that sum formed by torch in fp32, bit for bit; dgamma / dbeta (atomics across blocks) agree to
+    1e-4 of the max."""
+    x = rnd(R, d).to(DEV)
+    os_ = [rnd(R, d, seed=5 + m).to(DEV) for m in range(M)]
+    gam = [(rnd(d, seed=20 + m).abs() + 0.5).to(DEV) for m in range(M)]
+    bet = [rnd(d, seed=30 + m).to(DEV) for m in range(M)]
+    _, mean, rstd = ops.ln_fwd(x, os_, gam, bet, 1e-5, None, R)
+    dys = [rnd(R, d, seed=70 + i).to(DEV) for i in range(naddends)]
+    whole = dys[0] + dys[1]
+    if naddends == 3:
+        whole = whole + dys[2]
+
+    def run(dy):
+        dgs, dbs = [torch.zeros_like(g) for g in gam], [torch.zeros_like(b) for b in bet]
+        dx, d_o = ops.ln_bwd(x, os_, gam, bet, 1e-5, None, R, mean, rstd, dy, dgs, dbs)
+        return dx, d_o, dgs, dbs
+
+    dx, d_o, dgs, dbs = run(dys)
+    dx1, d_o1, dgs1, dbs1 = run(whole)
+    assert torch.equal(dx.view(torch.int32), dx1.view(torch.int32))
+    assert torch.equal(d_o.view(torch.int32), d_o1.view(torch.int32))
+    assert float(dx1.abs().max()) > 0 and float(d_o1.abs().max()) > 0
+    for a, b in zip(dgs + dbs, dgs1 + dbs1):
+        assert (a - b).abs().max().item() <= 1e-4 * max(b.abs().max().item(), 1.0)
+
+
+@pytest.mark.parametrize("with_coef", [False, True])
+@pytest.mark.parametrize("R", [511, 512, 513])
+def test_add_layernorm_three_branch_backward_at_the_kernel_switch(R, with_coef):
+    """M = 3, d = 256, one scene of R rows: one row below, at and above the row count from which the backward runs all
+    branches of a row in one wave (PQ3D_LN_MERGED_MIN_R = 512; 513 rows: the grid-stride tail of that kernel) -- gradients
+    against float64 autograd of the same expression."""
+    d, M = 256, 3
+    x = rnd(1, R, d)
+    os_ = [rnd(1, R, d, seed=5 + m) for m in range(M)]
+    gam = [rnd(d, seed=20 + m).abs() + 0.5 for m in range(M)]
+    bet = [rnd(d, seed=30 + m) for m in range(M)]
+    coef = torch.rand(M, 1, generator=torch.Generator().manual_seed(R)) + 0.1 if with_coef else None
+    leaves = [t.to(DEV).requires_grad_(True) for t in [x] + os_ + gam + bet]
+    y = ops.add_layernorm(leaves[0], leaves[1:1 + M], leaves[1 + M:1 + 2 * M], leaves[1 + 2 * M:], eps=1e-5,
+                          coef=coef.to(DEV) if with_coef else None, rows_per_scene=R)
+    refl = [t.clone().double().requires_grad_(True) for t in [x] + os_ + gam + bet]
+    yr = 0
+    for m in range(M):
+        w = coef[m].double()[:, None, None] if with_coef else 1.0 / M
+        yr = yr + w * O.layer_norm(refl[0] + refl[1 + m], refl[1 + M + m], refl[1 + 2 * M + m])
+    gy = rnd(1, R, d, seed=77)
+    y.backward(gy.to(DEV))
+    yr.backward(gy.double())
+    for i, (a, r) in enumerate(zip(leaves, refl)):
+        err = float((a.grad.double().cpu() - r.grad).abs().max()) / float(r.grad.abs().max())
+        assert err < 2e-5, (i, err)
+
+
 # ---------------------------------------------------------------------------------------------- misc
 def test_pairwise_locs_and_fourier_and_spatial_bias():
     c = torch.rand(2, 23, 3, generator=torch.Generator().manual_seed(11)) * 4

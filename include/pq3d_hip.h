@@ -1453,6 +1453,79 @@ int pq3d_scene_augment_apply(const float* coordinates, const float* colors, cons
                              const float* params, const void* ws, int64_t ws_bytes, const float* color_consts,
                              float* coordinates_out, float* features_out, int32_t* err, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Grounding (stage-2) batches from scans held on the device (csrc/object_prep.hip; the rules are restated in
+ * tests/object_prep_ref.py): the per-object point sets, boxes and label rows the reference builds per sample on the host
+ * (data/datasets/sceneverse_base.py).  Unlike the scene kernels above, every offsets array here is a DEVICE array and the
+ * number of scans S is unbounded (a batch of 128 samples may touch 128 scans).
+ *
+ * Object bank.  S scans concatenated: points [P, 6] fp32 (xyz | rgb), pt_off [S + 1] int64.  R object rows in all, the rows
+ * of scan s are [row_off[s], row_off[s + 1]); row r selects point p of its scan iff point2instance[p] == instance_ids[r]
+ * (ids form) or masks[mask_off[s] + (r - row_off[s]) * P_s + p] != 0 (masks form; pass the other form's pointers as NULL).
+ * A row is cut into cells of PQ3D_OBJECT_CHUNK points; cell_off [R + 1] int64 = first cell of every row (the host computes
+ * it: ceil(P_s / PQ3D_OBJECT_CHUNK) cells per row of scan s).  A scan has at most PQ3D_OBJECT_MAX_POINTS points and
+ * PQ3D_OBJECT_MAX_ROWS rows (checked by the caller).
+ *   pq3d_object_count  cnt [cells] int32 = selected points per cell, cbase [cells] = exclusive scan of cnt inside its row,
+ *                      row_total [R] = points per row.
+ *   pq3d_object_emit   order[row_entry[r] + j] = the j-th selected point of row r in ascending order (scan-local int32);
+ *                      row_entry [R + 1] int64 = exclusive scan of row_total (the caller's), E = row_entry[R] entries.
+ *   pq3d_object_boxes  O kept objects (entry_off [O + 1] int64 into order, obj_scan [O] int32, obj_off [S + 1] int32 = first
+ *                      object of every scan): convert_pc_to_box in fp32 -- box_center = (min + max) / 2, box_size = max - min.
+ * Integer arithmetic and exact min / max only: two runs give the same bits.
+ *
+ * pq3d_match_boxes: match_gt_to_pred.  G >= 1 GT boxes and K >= 0 predicted boxes as centre / size [*, 3] fp32; the IoU is
+ * box3d_iou's formula (inter / (v1 + v2 - inter + 1e-8)) on the corners c -+ s / 2, evaluated in fp64 without contraction.
+ * matched [G] int32 = first index of the strictly largest IoU (-1 when K = 0), iou25 / iou50 [G, K] bytes = IoU >= 0.25 / 0.5.
+ *
+ * pq3d_object_sample: one workgroup per (item, slot).  scene_of_item [B] int32, selected [B, O_max] int32 = object index
+ * local to the item's scan, -1 = padded slot; seed = device int64 word; rotation = NULL or [B, 3, 3] fp32 (xyz' = xyz x R).
+ * Draw j < num_points of an object of n points (key = hash of (seed, item, slot)): n >= num_points: perm(j), a keyed
+ * bijection of [0, n) (4-round balanced Feistel network over the smallest even bit width covering n, cycle-walking with a
+ * cap of PQ3D_OBJECT_WALK_CAP passes); n < num_points: (hash(key, j) * n) >> 32.  Then _obj_processing_post in fp64 with a
+ * fixed reduction tree, rounded to fp32 once: obj_fts [B, O_max, num_points, 6] = (xyz - mean) / max(max |xyz - mean|, 1e-6)
+ * | rgb, obj_locs [B, O_max, 6] = mean | size, obj_boxes = (min + max) / 2 | size, obj_pad_masks [B, O_max] bytes.  Padded
+ * slots are written as zeros.  1 <= num_points <= PQ3D_OBJECT_MAX_SAMPLE.  No host synchronisation: capturable, and a replay
+ * reads the seed word anew.
+ * err[0] (zeroed by the call; the slot of a bad index is written as padding, nothing is dereferenced through it):
+ *    1  scene_of_item outside [0, S)          2  selected outside [-1, objects of the scan)
+ *    4  a cycle walk hit its cap              8  (pq3d_ground_labels) a target outside [-1, GT objects of the scan)
+ *   16  the bank's own tables are inconsistent
+ *
+ * pq3d_ground_labels: labels [3, B, O_max] fp32 = the 0-1 rows tgt_object_id, tgt_object_id_iou25, tgt_object_id_iou50.
+ * targets [B, T_max] int32, -1 padded.  matched == NULL (gt form): slot q is 1 in all three iff selected[b, q] is a target.
+ * Otherwise (pred form) targets index the scan's GT objects and the tables are the scans' pq3d_match_boxes outputs
+ * concatenated (gt_off [S + 1] int32 into matched, tab_off [S + 1] int64 into iou25 / iou50, K_s = objects of scan s):
+ * row 0: matched[t] == selected[b, q] for a target t; rows 1, 2: the target's iou25 / iou50 bit of prediction selected[b, q].
+ * pq3d_object_range: coord_min / coord_max [B, 3] = min / max of obj_locs[:, :3] over the valid slots (zeros without one).
+ * pq3d_object_rows: out [B, O_max, D] = table[obj_off[scene] + selected[b, q]], zeros for padded slots.
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_OBJECT_MAX_POINTS (1 << 20)
+#define PQ3D_OBJECT_MAX_ROWS 1024
+#define PQ3D_OBJECT_CHUNK 1024
+#define PQ3D_OBJECT_MAX_SAMPLE 4096
+#define PQ3D_OBJECT_WALK_CAP 256
+int pq3d_object_count(const int64_t* pt_off, const int64_t* row_off, const int64_t* cell_off, const int64_t* point2instance,
+                      const int64_t* instance_ids, const uint8_t* masks, const int64_t* mask_off, int32_t S, int64_t R, int64_t cells,
+                      int32_t* cnt, int32_t* cbase, int32_t* row_total, void* stream);
+int pq3d_object_emit(const int64_t* pt_off, const int64_t* row_off, const int64_t* cell_off, const int64_t* point2instance,
+                     const int64_t* instance_ids, const uint8_t* masks, const int64_t* mask_off, int32_t S, int64_t R, int64_t cells,
+                     const int32_t* cbase, const int64_t* row_entry, int64_t E, int32_t* order, void* stream);
+int pq3d_object_boxes(const float* points, const int64_t* pt_off, const int32_t* obj_off, const int64_t* entry_off, const int32_t* order,
+                      int32_t S, const int32_t* obj_scan, int32_t O, float* box_center, float* box_size, void* stream);
+int pq3d_match_boxes(const float* gt_center, const float* gt_size, const float* pred_center, const float* pred_size, int32_t G, int32_t K,
+                     int32_t* matched, uint8_t* iou25, uint8_t* iou50, void* stream);
+int pq3d_object_sample(const float* points, const int64_t* pt_off, const int32_t* obj_off, const int64_t* entry_off, const int32_t* order,
+                       int32_t S, const int32_t* scene_of_item, const int32_t* selected, int32_t B, int32_t O_max, int32_t num_points,
+                       const int64_t* seed, const float* rotation, float* obj_fts, float* obj_locs, float* obj_boxes,
+                       uint8_t* obj_pad_masks, int32_t* err, void* stream);
+int pq3d_ground_labels(const int32_t* obj_off, int32_t S, const int32_t* scene_of_item, const int32_t* selected, const int32_t* targets,
+                       int32_t B, int32_t O_max, int32_t T_max, const int32_t* matched, const uint8_t* iou25, const uint8_t* iou50,
+                       const int32_t* gt_off, const int64_t* tab_off, float* labels, int32_t* err, void* stream);
+int pq3d_object_range(const float* obj_locs, const uint8_t* obj_pad_masks, int32_t B, int32_t O_max, float* coord_min, float* coord_max,
+                      void* stream);
+int pq3d_object_rows(const float* table, int32_t D, const int32_t* obj_off, int32_t S, const int32_t* scene_of_item,
+                     const int32_t* selected, int32_t B, int32_t O_max, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,4 +17,8 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
                 "check_instance_targets"):
         from . import scene
         return getattr(scene, name)
+    if name in ("build_object_bank", "match_boxes", "match_banks", "sample_objects", "ground_labels", "prepare_grounding_batch",
+                "check_objects"):
+        from . import objects
+        return getattr(objects, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1526,6 +1526,55 @@ int pq3d_object_range(const float* obj_locs, const uint8_t* obj_pad_masks, int32
 int pq3d_object_rows(const float* table, int32_t D, const int32_t* obj_off, int32_t S, const int32_t* scene_of_item,
                      const int32_t* selected, int32_t B, int32_t O_max, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 grounding: ground_loss and the device part of ScanReferEval / ReferIt3DEval / Multi3DReferEval (csrc/ground.hip,
+ * DESIGN 7g; the rules are restated in tests/ground_eval_ref.py).  Every array is a device array; no entry point reads
+ * device memory on the host or allocates, so all of them can be captured.  No floating-point atomics: two runs give the same
+ * bits.
+ *
+ * pq3d_bce_logits_fwd: cross_entropy's BCE branch (optim/loss/query3d_loss.py:10-16) in one launch.  x, y fp32 [N] (y in
+ * [0, 1]); c_i = x_i < -100 ? -100 : x_i (a NaN stays and reaches the loss);
+ *   loss[0] = weight * (sum_i max(c_i, 0) - c_i y_i + log1p(exp(-|c_i|))) / N  [+ addend[0]],
+ * log1p(exp(.)) in fp32, everything else in fp64 in a fixed order (one workgroup), rounded to fp32 once.  addend: NULL or a
+ * device scalar, as pq3d_cross_entropy_mean's.  1 <= N <= PQ3D_BCE_MAX_N.
+ * pq3d_bce_logits_bwd: dx_i = g[0] * weight / N * (sigmoid(x_i) - y_i) where x_i >= -100 (or NaN), exactly 0 where
+ * x_i < -100 (-inf included); evaluated in fp64, rounded to fp32 once.  g is a device scalar.
+ *
+ * pq3d_refer_counts: one launch, one workgroup.  logits [B, O] fp32; pred [B] int32 = argmax of the row as torch.argmax
+ * (NaN is maximal, ties go to the smallest index, a row of -inf gives 0).  labels: NULL or the rows pq3d_ground_labels writes,
+ * [3, B, O] fp32; tgt: NULL or [B] int64 target indices (at least one of the two).  Hit bits of item b, hits [B] bytes:
+ *   1  correct: tgt ? pred == tgt[b] : labels[0, b, pred] != 0       2 / 4  labels[1 / 2, b, pred] != 0 (0 without labels)
+ *   8  the item is counted: item_mask == NULL or item_mask[b] != 0
+ * counts [PQ3D_REFER_GROUPS, 4] int32 over the counted items: columns (items, correct, iou25, iou50); groups 0 all,
+ * 1 / 2 is_multiple set / clear, 3 / 4 is_hard set / clear, 5 / 6 is_view_dependent set / clear.  The flag rows are bytes [B];
+ * the two groups of a NULL row are 0.  3 * B * O < 2^31.
+ *
+ * Multi3DReferEval.evaluate_one_query, three launches: pq3d_ground_f1_cost, pq3d_lsap_batched (n_rows = n_cols = the third
+ * row of sizes, ld = n), pq3d_ground_f1_count.
+ * pq3d_ground_f1_cost: one workgroup per item.  logits [B, O] fp32, obj_boxes [B, O, 6] fp32 (centre | size), tgt_boxes
+ * [B, T_max, 6] FP64 (the reference keeps them as Python floats), n_tgt [B] int32.  Slot q is selected iff
+ * 1 / (1 + expf(-x)) > 0.5f; selected [B, O] int32 = the selected slots in slot order, -1 past them.  sizes [4, B] int32 =
+ * P (selected), G (= n_tgt), n_b = max(P, G), error bits.  cost [B, n, n] fp32, n = max(O, T_max) <= PQ3D_LSAP_MAX_DIM: inside
+ * the leading n_b x n_b block, -IoU(selected i, target j) for i < P, j < G and 0 elsewhere; NOTHING outside that block is
+ * written.  IoU = box3d_iou of the corners c -+ s / 2: the predicted box's corners and volume in fp32, the target's in fp64,
+ * intersection, union, + 1e-8 and the quotient in fp64, rounded to fp32; no contraction.
+ * pq3d_ground_f1_count: one wave per item.  out [B, 4] int32 = (tp25, tp50, P, G): assigned pairs (r, c) with r < P and
+ * -cost[r, c] >= 0.25f / 0.5f (compared in fp32).
+ * Error bits (sizes[3]; an item with one has P = G = n_b = 0 or counts of 0, nothing is indexed through the bad value):
+ *   1  n_tgt outside [0, T_max]     2  pq3d_lsap_batched reported an error     4  an assignment index or n_match out of range
+ * ------------------------------------------------------------------------------------------------ */
+#define PQ3D_BCE_MAX_N (1 << 24)
+#define PQ3D_REFER_GROUPS 7
+int pq3d_bce_logits_fwd(const float* x, const float* y, int64_t N, float weight, const float* addend, float* loss, void* stream);
+int pq3d_bce_logits_bwd(const float* x, const float* y, int64_t N, float weight, const float* g, float* dx, void* stream);
+int pq3d_refer_counts(const float* logits, const float* labels, const int64_t* tgt, const uint8_t* is_multiple, const uint8_t* is_hard,
+                      const uint8_t* is_view_dependent, const uint8_t* item_mask, int32_t B, int32_t O, int32_t* pred, uint8_t* hits,
+                      int32_t* counts, void* stream);
+int pq3d_ground_f1_cost(const float* logits, const float* obj_boxes, const double* tgt_boxes, const int32_t* n_tgt, int32_t B, int32_t O,
+                        int32_t T_max, float* cost, int32_t* sizes, int32_t* selected, void* stream);
+int pq3d_ground_f1_count(const float* cost, const int32_t* row_idx, const int32_t* col_idx, const int32_t* n_match,
+                         const int32_t* lsap_err, int32_t B, int32_t n, int32_t* sizes, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

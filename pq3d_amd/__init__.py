@@ -21,4 +21,7 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
                 "check_objects"):
         from . import objects
         return getattr(objects, name)
+    if name in ("refer_counts", "multi3drefer_counts", "ScanReferEval", "ReferIt3DEval", "Multi3DReferEval"):
+        from . import ground_eval
+        return getattr(ground_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -431,6 +431,12 @@ _SIGS = {
     "pq3d_object_range": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3,
     "pq3d_object_rows": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                          C.c_void_p],
+    # stage-2 grounding loss and the refer evaluators' counts (csrc/ground.hip); every array is a device array
+    "pq3d_bce_logits_fwd": [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_bce_logits_bwd": [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pq3d_refer_counts": [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4,
+    "pq3d_ground_f1_cost": [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 4,
+    "pq3d_ground_f1_count": [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3,
 }
 _RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
           "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows", "pq3d_scene_augment_ws_bytes"}   # size queries: bytes (or -1), not a status code

@@ -11,7 +11,11 @@ gradient launch and two cross-entropy launches.  No CPU fallback for the device 
 
 ``SetCriterion(..., matching="device")`` runs the assignments on the device instead (pq3d_amd/lsap.py: one launch for all
 layers and scenes, exactly scipy's result): the forward then makes no device-to-host transfer, and with padded targets
-(``SetCriterion.pad_targets``) decoder + criterion + backward can be captured into one graph."""
+(``SetCriterion.pad_targets``) decoder + criterion + backward can be captured into one graph.
+
+Stage 2 (configs/unified_tasks_sceneverse.yaml, ``loss_list: [ground_loss, generation_loss]``): ``bce_with_logits_mean`` (csrc/ground.hip,
+one launch each way), ``ground_loss``, ``generation_loss``, ``mask_loss`` and ``Query3DLoss``, the counterpart of optim/loss/loss.py's
+``Loss`` for those terms."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -474,6 +478,109 @@ class _RowCE(Function):
         L.call("pq3d_cross_entropy_bwd", ce)
         dl = dl.view(ctx.shape)
         return (dl if ctx.dtype == torch.float32 else dl.to(ctx.dtype)), None, None, (g if ctx.has_add else None)
+
+
+def bce_with_logits_mean(logits: torch.Tensor, labels: torch.Tensor, weight: float = 1.0,
+                         add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """weight * F.binary_cross_entropy_with_logits(torch.clamp(logits, min=-100), labels) [+ add] over all elements (the BCE
+    branch of the reference's cross_entropy, optim/loss/query3d_loss.py:10-16): one launch forward, one backward.  ``add`` as
+    in ``cross_entropy_rows``.  A logit below -100 (a padded slot's -inf) takes no gradient."""
+    return _BceMean.apply(logits, labels, float(weight), add)
+
+
+class _BceMean(Function):
+    """Like _RowCE: the loss in a 0-dim tensor of its own; weight, 1 / N and the upstream gradient meet inside the kernels."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, add=None):
+        assert add is None or (add.numel() == 1 and add.dtype == torch.float32 and add.is_cuda)
+        if logits.shape != labels.shape:
+            raise ValueError(f"logits {tuple(logits.shape)} and labels {tuple(labels.shape)} differ in shape")
+        x = logits.contiguous().float().view(-1)
+        y = labels.contiguous().float().view(-1)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)   # of its own: see _RowCE
+        L.call("pq3d_bce_logits_fwd", x, y, x.numel(), weight, add, loss)
+        ctx.save_for_backward(x, y)
+        ctx.weight, ctx.has_add, ctx.shape, ctx.dtype = weight, add is not None, logits.shape, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        scale = g.reshape(1)
+        if scale.dtype != torch.float32 or not scale.is_contiguous():
+            scale = scale.float().contiguous()
+        dx = torch.empty_like(x)
+        L.call("pq3d_bce_logits_bwd", x, y, x.numel(), ctx.weight, scale, dx)
+        dx = dx.view(ctx.shape)
+        return (dx if ctx.dtype == torch.float32 else dx.to(ctx.dtype)), None, None, (g if ctx.has_add else None)
+
+
+def _head_loss(data_dict, head: str, fallback=None, weight: float = 1.0, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """query3d_loss.py:10-24: cross_entropy(data_dict[head + '_logits'], data_dict[head + '_label'])."""
+    names = (head + "_logits", head + "_label")
+    if names[0] not in data_dict and fallback is not None:
+        names = fallback
+    logits, label = data_dict[names[0]], data_dict[names[1]]
+    if label is None:
+        raise KeyError(f"{names[1]} is missing: {head}_loss needs the labels of {names[0]}")
+    if label.shape == logits.shape:        # a 0-1 row per item: BCE over every slot, the padded ones included
+        return bce_with_logits_mean(logits, label, weight, add)
+    # index labels.  (The reference clamps here too; a row's log-sum-exp does not see a -inf turned into -100 unless the whole row
+    # is below -100 + log(eps), so the CE kernels take the logits as they are.)
+    ce = cross_entropy_rows(logits, label, -100, add if weight == 1.0 else None)
+    if weight == 1.0:
+        return ce
+    return ce * weight if add is None else ce * weight + add
+
+
+def ground_loss(data_dict, weight: float = 1.0, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The registry's 'ground_loss' (configs/unified_tasks_sceneverse.yaml: loss_list [ground_loss, generation_loss], weight 10):
+    ground_logits / ground_label, else og3d_logits / tgt_object_id."""
+    return _head_loss(data_dict, "ground", ("og3d_logits", "tgt_object_id"), weight, add)
+
+
+def generation_loss(data_dict, weight: float = 1.0, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The registry's 'generation_loss': token cross-entropy of the teacher-forced logits (ignore_index -100)."""
+    return _head_loss(data_dict, "generation", None, weight, add)
+
+
+class Query3DLoss(nn.Module):
+    """optim/loss/loss.py:113-152 (Loss) for the stage-2 terms ground_loss, generation_loss and mask_loss:
+    forward(data_dict) -> (total_loss, all_losses), every term times loss_weights.get(name, 1.0), total_loss = the sum over
+    loss_list (also all_losses['total_loss']).
+    ``total(data_dict)`` returns the same total alone and is what a training step wants (``TrainStep(model, crit.total)``): there
+    the terms are chained through the kernels' ``add`` operand, so the running total costs no elementwise launch where a term
+    has one (BCE with any weight, CE with weight 1); the sum is then rounded once per term from fp64 instead of added in fp32."""
+    TERMS = ("ground_loss", "generation_loss", "mask_loss")
+
+    def __init__(self, loss_list: Sequence[str], loss_weights: Optional[Dict[str, float]] = None, vis_loss_list: Sequence[str] = ()):
+        super().__init__()
+        self.selected_keys = list(loss_list)
+        self.all_keys = self.selected_keys + [k for k in vis_loss_list if k not in self.selected_keys]
+        unknown = [k for k in self.all_keys if k not in self.TERMS]
+        if unknown or not self.selected_keys:
+            raise NotImplementedError(f"loss terms {unknown or '(none)'}: Query3DLoss covers {', '.join(self.TERMS)}")
+        self.loss_weights = {k: float(v) for k, v in dict(loss_weights or {}).items()}
+
+    def _term(self, k, data_dict, add=None):
+        w = self.loss_weights.get(k, 1.0)
+        if k == "mask_loss":
+            cur = mask_loss(data_dict) * w
+            return cur if add is None else add + cur
+        return (ground_loss if k == "ground_loss" else generation_loss)(data_dict, w, add)
+
+    def forward(self, data_dict):
+        all_losses = {k: self._term(k, data_dict) for k in self.all_keys}
+        total = sum(all_losses[k] for k in self.selected_keys)
+        all_losses["total_loss"] = total
+        return total, all_losses
+
+    def total(self, data_dict) -> torch.Tensor:
+        total = None
+        for k in self.selected_keys:
+            total = self._term(k, data_dict, total)
+        return total
 
 
 class DirectCriterion(nn.Module):

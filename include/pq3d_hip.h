@@ -292,9 +292,11 @@ int pq3d_attn_resident(int enable);
  *   pq3d_mask_not      : dst_g[i] = !src_g[i] for up to PQ3D_MAX_GROUPS byte masks of individual lengths (data_dict's
  *                        'True = valid' pad masks -> PyTorch's 'True = ignore', query3d_unified.py:113,139,143,148,155)
  *   pq3d_zero_many     : zero-fill n fp32 buffers (gradient arena, atomics targets)
- *   pq3d_sum_n         : out = sum_g src_g, fixed order (d query_pos over the layers)
+ *   pq3d_sum_n         : out = sum_g src_g, fixed order (d query_pos over the layers); any count, any alignment (float4
+ *                        pieces when out and every src_g are 16-byte aligned, element by element otherwise and for the
+ *                        last count % 4 elements; the same left-to-right order either way)
  *   pq3d_mean_all      : out[0] = mean(x): per-block partial sums + last-arriver combine in block order (deterministic,
- *                        one launch; ws = counter + partials, self-resetting); pq3d_fill_scaled: dst[i] = scalar[0] * c
+ *                        one launch; ws = counter + partials, self-resetting; x of any alignment); pq3d_fill_scaled: dst[i] = scalar[0] * c
  *                        (its gradient) -- the synthetic 'mean(query)' loss of SURVEY 8d
  *   pq3d_cast_transpose: src_g [rows, cols] fp32 -> out_g bf16 (same layout) and outT_g bf16 with every cols x cols row
  *                        block transposed (outT[t][k][n] = src[t cols + n][k]): the K/V projection weights once per step

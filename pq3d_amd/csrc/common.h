@@ -130,8 +130,10 @@ PQ_DEV float load_elem(const void* base, int dt, long idx) {
 
 PQ_DEV float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 PQ_DEV float qgelu_f(float x) { return x / (1.f + expf(-1.702f * x)); }   // x sigmoid(1.702 x): CLIP's quick_gelu (forward only)
+// Phi(x) + x phi(x).  Phi as erfc(-x / sqrt 2) / 2: 1 + erf(..) cancels to nothing below x ~ -5.5 (erff returns -1), which left
+// the derivative's negative tail with x phi(x) alone, 3 % off at x = -6; erfcf keeps the tail to a few ulp
 PQ_DEV float gelu_grad_f(float x) {
-  return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
+  return 0.5f * erfcf(x * -0.70710678118654752f) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
 
 // Kernel-argument prefetch (see gemm_fast_kernel in gemm.hip): one empty asm statement that "uses" every descriptor

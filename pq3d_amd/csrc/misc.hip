@@ -447,33 +447,36 @@ __global__ void mask_not_kernel(const NotPtrs p) {
 }
 
 struct SumPtrs { const float* src[PQ3D_MAX_GROUPS]; };
-__global__ void sum_n_kernel(const SumPtrs p, int n, float* out, long cnt) {   // out = sum_g src_g (fixed order)
-  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < cnt; i += (long)gridDim.x * blockDim.x * 4) {
-    float4 a = *(const float4*)(p.src[0] + i);
-    for (int g = 1; g < n; ++g) {
-      const float4 b = *(const float4*)(p.src[g] + i);
-      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+// out[i .. i + 4) = sum_g src_g[i .. i + 4), the parts added left to right; vec: every pointer 16-byte aligned (one float4 per
+// part), otherwise -- and for the last cnt % 4 elements -- element by element in the same order
+PQ_DEV void sum_quads(const float* const* src, int n, float* out, long cnt, bool vec, long i0, long stride) {
+  for (long i = i0; i < cnt; i += stride) {
+    if (vec && i + 3 < cnt) {
+      float4 a = *(const float4*)(src[0] + i);
+      for (int g = 1; g < n; ++g) {
+        const float4 b = *(const float4*)(src[g] + i);
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+      }
+      *(float4*)(out + i) = a;
+    } else {
+      for (long j = i; j < min(i + 4, cnt); ++j) {
+        float a = src[0][j];
+        for (int g = 1; g < n; ++g) a += src[g][j];
+        out[j] = a;
+      }
     }
-    *(float4*)(out + i) = a;
   }
+}
+__global__ void sum_n_kernel(const SumPtrs p, int n, float* out, long cnt, int vec) {   // out = sum_g src_g (fixed order)
+  sum_quads(p.src, n, out, cnt, vec != 0, ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4, (long)gridDim.x * blockDim.x * 4);
 }
 
 // two sums of different lengths in one launch (blockIdx.y selects the job)
-struct SumPair { SumPtrs p[2]; int n[2]; float* out[2]; long cnt[2]; };
+struct SumPair { SumPtrs p[2]; int n[2]; float* out[2]; long cnt[2]; int vec[2]; };
 __global__ void sum_pair_kernel(const SumPair q) {
   const int y = blockIdx.y;
-  const float* const* src = q.p[y].src;
-  const int n = q.n[y];
-  float* out = q.out[y];
-  const long cnt = q.cnt[y];
-  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < cnt; i += (long)gridDim.x * blockDim.x * 4) {
-    float4 a = *(const float4*)(src[0] + i);
-    for (int g = 1; g < n; ++g) {
-      const float4 b = *(const float4*)(src[g] + i);
-      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    *(float4*)(out + i) = a;
-  }
+  sum_quads(q.p[y].src, q.n[y], q.out[y], q.cnt[y], q.vec[y] != 0, ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4,
+            (long)gridDim.x * blockDim.x * 4);
 }
 
 // mean of all elements, one launch: every block reduces a slice (float4 loads, all in flight), publishes its partial sum,
@@ -484,11 +487,15 @@ __global__ __launch_bounds__(256) void mean_all_kernel(const float* x, long n, f
   __shared__ int last;
   const long n4 = n >> 2;
   float s = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const float4 v = ((const float4*)x)[i];
-    s += (v.x + v.y) + (v.z + v.w);
+  if ((((uintptr_t)x) & 15) == 0) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+      const float4 v = ((const float4*)x)[i];
+      s += (v.x + v.y) + (v.z + v.w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) s += x[(n4 << 2) + threadIdx.x];
+  } else {   // a contiguous view that starts inside a 16-byte piece: element by element
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += x[i];
   }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) s += x[(n4 << 2) + threadIdx.x];
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -700,15 +707,17 @@ extern "C" int pq3d_copy_many(const float* const* src, float* const* dst, const 
 
 extern "C" int pq3d_sum_n(const float* const* src, int32_t n, float* out, int64_t count, void* stream) {
   PQ_DEVICE_GUARD(stream, nullptr);
-  PQ_CHECK_ARG(src && out && n >= 1 && n <= PQ3D_MAX_GROUPS && count >= 0 && (count % 4) == 0, "pq3d_sum_n: bad args (count % 4 == 0)");
+  PQ_CHECK_ARG(src && out && n >= 1 && n <= PQ3D_MAX_GROUPS && count >= 0, "pq3d_sum_n: bad args");
   SumPtrs p;
+  uintptr_t bits = (uintptr_t)out;
   for (int g = 0; g < n; ++g) {
-    PQ_CHECK_ARG(src[g] && ((((uintptr_t)src[g]) & 15) == 0), "pq3d_sum_n: inputs must be 16-byte aligned");
+    PQ_CHECK_ARG(src[g], "pq3d_sum_n: null input");
     p.src[g] = src[g];
+    bits |= (uintptr_t)src[g];
   }
-  PQ_CHECK_ARG((((uintptr_t)out) & 15) == 0, "pq3d_sum_n: out must be 16-byte aligned");
   if (count == 0) return 0;
-  hipLaunchKernelGGL(sum_n_kernel, dim3(grid1d(count / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, p, n, out, (long)count);
+  hipLaunchKernelGGL(sum_n_kernel, dim3(grid1d((count + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, p, n, out, (long)count,
+                     (int)((bits & 15) == 0));
   PQ_LAUNCH_CHECK();
   return 0;
 }
@@ -717,22 +726,24 @@ extern "C" int pq3d_sum_pair(const float* const* src_a, int32_t na, float* out_a
                              int32_t nb, float* out_b, int64_t count_b, void* stream) {
   PQ_DEVICE_GUARD(stream, nullptr);
   PQ_CHECK_ARG(src_a && src_b && out_a && out_b && na >= 1 && nb >= 1 && na <= PQ3D_MAX_GROUPS && nb <= PQ3D_MAX_GROUPS &&
-                   count_a >= 0 && count_b >= 0 && (count_a % 4) == 0 && (count_b % 4) == 0,
-               "pq3d_sum_pair: bad args (counts % 4 == 0)");
+                   count_a >= 0 && count_b >= 0, "pq3d_sum_pair: bad args");
   SumPair q;
+  uintptr_t bits_a = (uintptr_t)out_a, bits_b = (uintptr_t)out_b;
   for (int g = 0; g < na; ++g) {
-    PQ_CHECK_ARG(src_a[g] && ((((uintptr_t)src_a[g]) & 15) == 0), "pq3d_sum_pair: inputs must be 16-byte aligned");
+    PQ_CHECK_ARG(src_a[g], "pq3d_sum_pair: null input");
     q.p[0].src[g] = src_a[g];
+    bits_a |= (uintptr_t)src_a[g];
   }
   for (int g = 0; g < nb; ++g) {
-    PQ_CHECK_ARG(src_b[g] && ((((uintptr_t)src_b[g]) & 15) == 0), "pq3d_sum_pair: inputs must be 16-byte aligned");
+    PQ_CHECK_ARG(src_b[g], "pq3d_sum_pair: null input");
     q.p[1].src[g] = src_b[g];
+    bits_b |= (uintptr_t)src_b[g];
   }
-  PQ_CHECK_ARG(((((uintptr_t)out_a) | ((uintptr_t)out_b)) & 15) == 0, "pq3d_sum_pair: outputs must be 16-byte aligned");
   q.n[0] = na; q.n[1] = nb; q.out[0] = out_a; q.out[1] = out_b; q.cnt[0] = count_a; q.cnt[1] = count_b;
+  q.vec[0] = (bits_a & 15) == 0; q.vec[1] = (bits_b & 15) == 0;
   const long big = count_a > count_b ? count_a : count_b;
   if (big == 0) return 0;
-  hipLaunchKernelGGL(sum_pair_kernel, dim3(grid1d(big / 4, 256, 1024), 2), dim3(256), 0, (hipStream_t)stream, q);
+  hipLaunchKernelGGL(sum_pair_kernel, dim3(grid1d((big + 3) / 4, 256, 1024), 2), dim3(256), 0, (hipStream_t)stream, q);
   PQ_LAUNCH_CHECK();
   return 0;
 }
@@ -740,7 +751,6 @@ extern "C" int pq3d_sum_pair(const float* const* src_a, int32_t na, float* out_a
 extern "C" int pq3d_mean_all(const float* x, int64_t n, float* out, float* ws, void* stream) {
   PQ_DEVICE_GUARD(stream, x);
   PQ_CHECK_ARG(x && out && ws && n >= 1, "pq3d_mean_all: bad args");
-  PQ_CHECK_ARG((((uintptr_t)x) & 15) == 0, "pq3d_mean_all: x must be 16-byte aligned");
   long nb = (n / 4 + 255) / 256;
   if (nb > PQ3D_MEAN_MAX_BLOCKS) nb = PQ3D_MEAN_MAX_BLOCKS;
   if (nb < 1) nb = 1;
@@ -808,7 +818,7 @@ extern "C" int pq3d_cast_transpose(const float* const* src, void* const* out, vo
 
 extern "C" int pq3d_colsum(const void* x, int32_t dt, int64_t R, int64_t N, int64_t ld, float* out, void* stream) {
   PQ_DEVICE_GUARD(stream, x);
-  PQ_CHECK_ARG(x && out && R >= 0 && N >= 1 && ld >= N, "pq3d_colsum: bad args");
+  PQ_CHECK_ARG((x || R == 0) && out && R >= 0 && N >= 1 && ld >= N, "pq3d_colsum: bad args");   // no rows: x may be NULL, out = 0
   const void* xs[1] = {x};
   float* outs[1] = {out};
   return pq3d_colsum_grouped(xs, outs, 1, dt, R, N, ld, 0, stream);
@@ -821,7 +831,7 @@ extern "C" int pq3d_colsum_grouped(const void* const* x, float* const* out, int3
                "pq3d_colsum_grouped: bad args");
   ColsumPtrs cp;
   for (int g = 0; g < groups; ++g) {
-    PQ_CHECK_ARG(x[g] && out[g], "pq3d_colsum_grouped: null pointer");
+    PQ_CHECK_ARG((x[g] || R == 0) && out[g], "pq3d_colsum_grouped: null pointer");
     cp.x[g] = x[g]; cp.out[g] = out[g];
   }
   hipStream_t s = (hipStream_t)stream;
@@ -986,8 +996,9 @@ extern "C" int pq3d_pairwise_locs(const float* centers, int64_t center_stride, f
 extern "C" int pq3d_fourier(const float* xyz, int64_t xyz_stride, const float* cmin, const float* cmax,
                             const float* gauss_B, float* out, int32_t B, int32_t N, int32_t half, void* stream) {
   PQ_DEVICE_GUARD(stream, xyz);
-  PQ_CHECK_ARG(xyz && cmin && cmax && gauss_B && out && xyz_stride >= 3 && half >= 1, "pq3d_fourier: bad args");
-  if (B == 0 || N == 0) return 0;
+  PQ_CHECK_ARG(cmin && cmax && gauss_B && xyz_stride >= 3 && half >= 1 && B >= 0 && N >= 0, "pq3d_fourier: bad args");
+  if (B == 0 || N == 0) return 0;   // an empty point set has no storage: xyz and out may be NULL
+  PQ_CHECK_ARG(xyz && out, "pq3d_fourier: null pointer");
   hipLaunchKernelGGL(fourier_kernel, dim3(grid1d((long)B * N * half)), dim3(256), 0, (hipStream_t)stream, xyz,
                      (long)xyz_stride, cmin, cmax, gauss_B, out, B, N, half);
   PQ_LAUNCH_CHECK();
@@ -998,9 +1009,10 @@ extern "C" int pq3d_fourier_pair(const float* xyz_a, int64_t stride_a, int32_t N
                                  int32_t Nb, const float* cmin, const float* cmax, const float* gauss_B, float* out,
                                  int32_t B, int32_t half, void* stream) {
   PQ_DEVICE_GUARD(stream, xyz_a);
-  PQ_CHECK_ARG(xyz_a && xyz_b && cmin && cmax && gauss_B && out && stride_a >= 3 && stride_b >= 3 && half >= 1 && Na >= 0 &&
-                   Nb >= 0, "pq3d_fourier_pair: bad args");
+  PQ_CHECK_ARG(cmin && cmax && gauss_B && stride_a >= 3 && stride_b >= 3 && half >= 1 && Na >= 0 && Nb >= 0 && B >= 0,
+               "pq3d_fourier_pair: bad args");
   if (B == 0 || Na + Nb == 0) return 0;
+  PQ_CHECK_ARG((xyz_a || Na == 0) && (xyz_b || Nb == 0) && out, "pq3d_fourier_pair: null pointer");   // an empty set has no storage
   PQ_CHECK_ARG((long)B * (Na + Nb) < (1L << 30), "pq3d_fourier_pair: too many rows");
   const int rpb_ = half < 256 ? 256 / half : 1;
   hipLaunchKernelGGL(fourier_pair_kernel, dim3(grid1d(((long)B * (Na + Nb) + rpb_ - 1) / rpb_, 1, 65535)), dim3(256), 0, (hipStream_t)stream, xyz_a,

@@ -227,6 +227,8 @@ def pairwise_locs(centers: torch.Tensor, eps: float = 1e-10) -> torch.Tensor:
 
 def fourier(xyz: torch.Tensor, cmin: torch.Tensor, cmax: torch.Tensor, gauss_B: torch.Tensor, out=None) -> torch.Tensor:
     """Fourier features [sin | cos] of normalised coordinates (position_embedding.py:127-156); no grad."""
+    if xyz.numel() == 0:     # an empty point set: its strides carry no meaning (they may all be 0)
+        xyz = xyz.new_empty(xyz.shape)
     assert xyz.dtype == torch.float32 and xyz.stride(-1) == 1
     B, N = xyz.shape[:2]
     if xyz.stride(0) != N * xyz.stride(1):
@@ -241,6 +243,8 @@ def fourier(xyz: torch.Tensor, cmin: torch.Tensor, cmax: torch.Tensor, gauss_B: 
 def fourier_pair(xyz_a: torch.Tensor, xyz_b: torch.Tensor, cmin, cmax, gauss_B) -> torch.Tensor:
     """fourier() of two point sets of the same scenes in one launch: [B*Na + B*Nb, 2*half], set a's rows first."""
     def prep(x):
+        if x.numel() == 0:     # an empty set (as in fourier())
+            x = x.new_empty(x.shape)
         assert x.dtype == torch.float32 and x.stride(-1) == 1
         return x if x.stride(0) == x.shape[1] * x.stride(1) else x.contiguous()
     xyz_a, xyz_b = prep(xyz_a), prep(xyz_b)
@@ -291,7 +295,9 @@ def copy_many(dsts: Sequence[torch.Tensor], srcs: Sequence[torch.Tensor]) -> Non
 
 
 def sum_n(parts: Sequence[torch.Tensor]) -> torch.Tensor:
-    """sum of same-shape fp32 tensors in a fixed order, one launch (replaces torch.stack(..).sum(0): cat + reduce)."""
+    """sum of same-shape fp32 tensors in a fixed order (left to right), one launch per 31 parts (replaces
+    torch.stack(..).sum(0): cat + reduce).  Any element count and any contiguous view: parts that are not all 16-byte aligned
+    are added element by element, in the same order."""
     parts = [p.contiguous() for p in parts]
     if len(parts) == 1:
         return parts[0]
@@ -307,9 +313,11 @@ def sum_n(parts: Sequence[torch.Tensor]) -> torch.Tensor:
 
 def sum_pair(parts_a: Sequence[torch.Tensor], parts_b: Sequence[torch.Tensor]):
     """(sum_n(parts_a), sum_n(parts_b)) in one launch, the two results ADJACENT in one buffer (a first): a consumer that
-    wants their row concatenation (_SplitRows.backward) finds it already formed."""
+    wants their row concatenation (_SplitRows.backward) finds it already formed.  Element counts need not be multiples of 4
+    (b then starts inside a 16-byte piece and is added element by element).  More than 32 parts on a side: two sum_n calls,
+    the results not adjacent."""
     parts_a, parts_b = [p.contiguous() for p in parts_a], [p.contiguous() for p in parts_b]
-    if len(parts_a) > L.MAXG or len(parts_b) > L.MAXG or parts_a[0].numel() % 4 or parts_b[0].numel() % 4:
+    if len(parts_a) > L.MAXG or len(parts_b) > L.MAXG:
         return sum_n(parts_a), sum_n(parts_b)
     na, nb = parts_a[0].numel(), parts_b[0].numel()
     buf = torch.empty(na + nb, dtype=torch.float32, device=parts_a[0].device)

@@ -890,6 +890,32 @@ int pq3d_ap_pack(const int32_t* out, const void* plan, int64_t N, int64_t NG, co
                  int64_t max_entries, int32_t* packed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Box matching of detection AP (eval_det_cls, common/eval_det.py:107-193) for a batch of B ragged scenes, one launch, one
+ * workgroup per scene (pq3d_amd/csrc/instseg_box.hip; the host side is pq3d_amd/instseg_eval.py).
+ * pq3d_box_match: scene b's detections are rows [koff[b], koff[b+1]) of pboxes [NK, 6] fp32 (centre | extent), pclasses [NK]
+ * int64, pscores [NK] fp32, pvalid [NK] bytes (0 = the row is no detection); its GT boxes rows [goff[b], goff[b+1]) of
+ * gboxes [NG, 6] fp32, glabels [NG] int64, gvalid [NG] bytes.  koff / goff: device int64 [B+1]; at most PQ3D_AP_MAX_K
+ * detections and max_g <= PQ3D_BOX_MAX_G GT rows per scene (max_g sizes the LDS winner table).  thresholds: device fp64 [T],
+ * 1 <= T <= PQ3D_BOX_MAX_T.  Per valid detection, over the valid GT rows of its scene whose label equals its class, in row
+ * order: ovmax [NK] fp64 = the first maximum under a strict > of calc_iou (-inf without such a row), jmax [NK] int32 = that
+ * row's scene-local index (-1).  calc_iou on fp64 copies of the fp32 boxes: corners c -+ l / 2; 0 unless min(max_a, max_b) >
+ * max(min_a, min_b) strictly on all three axes; inter = (d0 * d1) * d2, vol = (l0 * l1) * l2, inter / ((vol_a + vol_b) -
+ * inter); no contraction.  flags [NK] bytes: bit t is set iff ovmax > thresholds[t] and the detection is the first by
+ * (-score, row) among its scene's detections with the same jmax and ovmax > thresholds[t] (ties of the score go to the lower
+ * row; the input need not be sorted).  Invalid rows get -inf, -1, 0.
+ * Error bits (err [1] int32, zeroed by the call; nothing is indexed through a bad value):
+ *   1  a NaN score          2  a non-finite prediction box coordinate      (the detection is a false positive: -inf, -1, 0)
+ *   4  a non-finite GT box coordinate (the row is left out of the matching)
+ *   8  koff / goff not ascending inside [0, NK] / [0, NG] or a scene over the limits (the scene's outputs are not written)
+ * No floating-point atomics, no allocation, no host read: capturable, bit-identical run to run. */
+#define PQ3D_BOX_MAX_G 4096
+#define PQ3D_BOX_MAX_T 4
+int pq3d_box_match(const float* pboxes, const int64_t* pclasses, const float* pscores, const uint8_t* pvalid, const int64_t* koff,
+                   int64_t NK, const float* gboxes, const int64_t* glabels, const uint8_t* gvalid, const int64_t* goff, int64_t NG,
+                   const double* thresholds, int32_t T, int32_t B, int32_t max_g, double* ovmax, int32_t* jmax, uint8_t* flags,
+                   int32_t* err, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer side of the training step around the path: what Query3DTrainer.backward does after
  * loss.backward() (trainer/query3d_trainer.py:18-28): clip_grad_norm_(grad_norm) (trainer/build.py:144-145),
  * torch.optim.AdamW.step() with the parameter groups of optim/utils.py:1-18 (weight decay 0.01 except biases /

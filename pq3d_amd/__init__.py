@@ -24,4 +24,7 @@ def __getattr__(name):   # lazy: importing the package stays free of torch-side 
     if name in ("refer_counts", "multi3drefer_counts", "ScanReferEval", "ReferIt3DEval", "Multi3DReferEval"):
         from . import ground_eval
         return getattr(ground_eval, name)
+    if name in ("box_match", "BoxAP", "InstSegEval"):
+        from . import instseg_eval
+        return getattr(instseg_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -437,6 +437,8 @@ _SIGS = {
     "pq3d_refer_counts": [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4,
     "pq3d_ground_f1_cost": [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 4,
     "pq3d_ground_f1_count": [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3,
+    # box matching of detection AP (csrc/instseg_box.hip); every array is a device array
+    "pq3d_box_match": [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 5,
 }
 _RET64 = {"pq3d_segment_plan_bytes", "pq3d_segment_ws_bytes", "pq3d_allreduce_wire_scratch_bytes", "pq3d_dbscan_ws_bytes",
           "pq3d_sparse_conv_wgrad_ws_bytes", "pq3d_bn_ws_floats", "pq3d_fps_scene_rows", "pq3d_scene_augment_ws_bytes"}   # size queries: bytes (or -1), not a status code

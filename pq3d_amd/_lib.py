@@ -2,23 +2,57 @@
 a call fails, a Pq3dError is raised -- the product path never routes through torch math or the oracle."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
-from typing import Optional, Sequence
+import re
+from typing import Mapping, Optional, Sequence
 
 import torch
 
 from .profiler import timed
 
-F32, BF16, BF16X3 = 0, 1, 2
-ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "add": 3, "planes": 4, "quick_gelu": 5}   # quick_gelu: forward only (act, never act_grad)
-MAXG = 32
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PQ3D_LIB_PATH") or os.path.join(_HERE, "libpq3d_hip.so")   # override: A/B builds of the kernels
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "pq3d_hip.h"))
 
 
 class Pq3dError(RuntimeError):
     pass
+
+
+def header_constants(text: str):
+    """The integer ``#define PQ3D_<NAME> <value>`` constants of a C header's text as a named tuple (read-only; ``_asdict()``: the
+    table).  A value is an integer literal, optionally negated, optionally ``a << b``, optionally parenthesised; a PQ3D_* define
+    of another form raises Pq3dError, so that whoever adds one decides how the host sees it."""
+    table = {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PQ3D_\w+)[ \t]*(.*?)[ \t]*$", text, flags=re.M):
+        m = re.fullmatch(r"(\()?\s*(-?)\s*(0[xX][0-9a-fA-F]+|[0-9]+)\s*(?:<<\s*([0-9]+)\s*)?(?(1)\))", value)
+        if value and m is None:
+            raise Pq3dError(f"{name}: the host reads an integer, -a, a << b or one of these in parentheses, not {value!r}")
+        if value:                                  # (the include guard has none)
+            table[name] = (-1 if m[2] else 1) * (int(m[3], 0) << int(m[4] or 0))
+    return collections.namedtuple("Header", table)(**table)
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        H = header_constants(_f.read())            # include/pq3d_hip.h: used as H.PQ3D_MAX_GROUPS
+except OSError as _e:
+    raise Pq3dError(f"{HEADER_PATH} not found: the host takes its limits and codes from the public header") from _e
+F32, BF16, BF16X3 = H.PQ3D_F32, H.PQ3D_BF16, H.PQ3D_BF16X3
+ACT = {None: H.PQ3D_ACT_NONE, "none": H.PQ3D_ACT_NONE, "relu": H.PQ3D_ACT_RELU, "gelu": H.PQ3D_ACT_GELU, "add": H.PQ3D_ACT_ADD,
+       "planes": H.PQ3D_ACT_PLANES, "quick_gelu": H.PQ3D_ACT_QGELU}   # quick_gelu: forward only (act, never act_grad)
+MAXG, MAX_OPT_SEGMENTS, TT_MAX_PROBLEMS = H.PQ3D_MAX_GROUPS, H.PQ3D_MAX_OPT_SEGMENTS, H.PQ3D_TT_MAX_PROBLEMS
+SCHED = {"constant": H.PQ3D_SCHED_CONSTANT, "warmup_cosine": H.PQ3D_SCHED_WARMUP_COSINE, "warmup_exp": H.PQ3D_SCHED_WARMUP_EXP}
+SUMSQ_PARTIALS = H.PQ3D_SUMSQ_PARTIALS
+
+
+def raise_error_word(who: str, word: int, messages: Mapping[int, str]) -> None:
+    """A kernel's error word on the host: ValueError with the text of every set bit, in the table's order; 0 passes."""
+    if word:
+        raise ValueError(f"{who}: " + "; ".join(m for bit, m in messages.items() if word & bit))
 
 
 class Dropout(C.Structure):
@@ -47,9 +81,6 @@ def set_drop(field: Dropout, drop: Optional["Drop"]) -> None:
         field.p, field.site, field.seed = drop.p, drop.site & 0xFFFFFFFF, ptr(drop.seed)
 
 
-MAX_OPT_SEGMENTS = 16
-
-
 class OptSegments(C.Structure):
     _fields_ = [("n", C.c_int32), ("end", C.c_int64 * MAX_OPT_SEGMENTS), ("lr_mul", C.c_float * MAX_OPT_SEGMENTS),
                 ("weight_decay", C.c_float * MAX_OPT_SEGMENTS)]
@@ -60,10 +91,6 @@ class AdamWHp(C.Structure):
                 ("max_grad_norm", C.c_float), ("sched", C.c_int32),
                 ("warmup_steps", C.c_int32), ("total_steps", C.c_int32), ("sched_gamma", C.c_float),
                 ("sched_stride", C.c_int32)]
-
-
-SCHED = {"constant": 0, "warmup_cosine": 1, "warmup_exp": 2}
-SUMSQ_PARTIALS = 1024
 
 
 class MaskPrepDesc(C.Structure):
@@ -87,9 +114,6 @@ class MaskGradDesc(C.Structure):
                 ("sig", C.c_void_p), ("T", C.c_void_p), ("TXS", C.c_void_p), ("sig_sum", C.c_void_p), ("t_sum", C.c_void_p),
                 ("seg_len", C.c_void_p), ("q_idx", C.c_void_p), ("t_idx", C.c_void_p), ("n_match", C.c_void_p),
                 ("g", C.c_void_p), ("dX", C.c_void_p * MAXG)]
-
-
-TT_MAX_PROBLEMS = 56
 
 
 class TtProblem(C.Structure):

@@ -77,7 +77,7 @@ def desc(q, k, v, o, lse, H, ct, zero_attn, *, scale=None, kpm=None, mask=None, 
     if grads is not None:
         d.dout, d.dq, d.dk, d.dv, d.delta, d.dbias = map(L.ptr, grads)
     if proj_dout is not None:
-        d.proj.mode, d.proj.dm, d.proj.x, d.proj.w[0] = 2, dm, L.ptr(proj_dout[0]), L.ptr(proj_dout[1])
+        d.proj.mode, d.proj.dm, d.proj.x, d.proj.w[0] = L.H.PQ3D_ATTN_PROJ_DOUT, dm, L.ptr(proj_dout[0]), L.ptr(proj_dout[1])
     ks = key_splits(B, H, Lq, Lk, dh, ct, q.dtype, bwd=grads is not None, bias=bias is not None, mask=mask is not None,
                     planes=planes is not None)
     ws = torch.empty(ws_elems(ks, B, H, Lq, dh), dtype=torch.float32, device=q.device) if ks > 1 else None

@@ -25,7 +25,7 @@ from .modules import SelfAttentionLayer, _PostNormBase, get_mlp_head, layer_repe
 VIT_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
                     max_position_embeddings=77, projection_dim=768, hidden_act="quick_gelu", layer_norm_eps=1e-5)
 DROP_BASE_TXT_ENC = 8 << 20
-ATTN_CAUSAL_MAX_T = 77   # PQ3D_ATTN_CAUSAL_MAX_T (include/pq3d_hip.h)
+ATTN_CAUSAL_MAX_T = L.H.PQ3D_ATTN_CAUSAL_MAX_T
 # module compute mode -> (GEMM compute type, dtype of the frozen weight copies and of the MFMA-operand activations).  'bf16x3'
 # forms every product of the tower split-bf16 from fp32 operands (fp32-grade); the residual stream, LayerNorm, softmax and the
 # normalisation are fp32 in every mode.

@@ -21,6 +21,7 @@ from . import _lib as L
 from .lsap import MAX_DIM, linear_sum_assignment_batched
 
 GROUPS = ("all", "multiple", "unique", "hard", "easy", "view_dep", "view_indep")      # rows of the count table
+assert len(GROUPS) == L.H.PQ3D_REFER_GROUPS, "the kernels count another number of groups than the host names"
 COLUMNS = ("items", "correct", "iou25", "iou50")
 HIT_CORRECT, HIT_IOU25, HIT_IOU50, HIT_COUNTED = 1, 2, 4, 8
 ERR_N_TGT, ERR_LSAP, ERR_INDEX = 1, 2, 4

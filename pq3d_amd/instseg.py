@@ -46,12 +46,9 @@ import torch
 from . import _lib as L
 from .ops import SegmentPlan
 
-SEG_CHUNK = 64           # PQ3D_INSTSEG_SEG_CHUNK
-PT_CHUNK = 256           # PQ3D_INSTSEG_PT_CHUNK
-MAX_K = 1024             # PQ3D_INSTSEG_MAX_K
-BOX_PART_BYTES = 64      # PQ3D_INSTSEG_BOX_PART_BYTES
-GRID_WORDS = 8           # PQ3D_DBSCAN_GRID_WORDS
-MAX_CELLS = 1 << 24      # PQ3D_DBSCAN_MAX_CELLS: cells of a DBSCAN call's grid over the batch (24-bit cell keys)
+SEG_CHUNK, PT_CHUNK, MAX_K = L.H.PQ3D_INSTSEG_SEG_CHUNK, L.H.PQ3D_INSTSEG_PT_CHUNK, L.H.PQ3D_INSTSEG_MAX_K
+BOX_PART_BYTES, GRID_WORDS = L.H.PQ3D_INSTSEG_BOX_PART_BYTES, L.H.PQ3D_DBSCAN_GRID_WORDS
+MAX_CELLS = L.H.PQ3D_DBSCAN_MAX_CELLS      # cells of a DBSCAN call's grid over the batch (24-bit cell keys)
 _ERRORS = {1: "voxel2segment holds ids outside [0, S)",
            2: "voxel_to_full_maps holds ids outside [0, number of voxels of the scene)",
            4: "segment_to_full_maps holds negative ids",
@@ -186,8 +183,7 @@ def instance_predictions(pred_logits: torch.Tensor, pred_masks: torch.Tensor, vo
 
 
 def _check_stats(err: int, sf: int, B: int) -> int:
-    if err:
-        raise ValueError("instance_predictions: " + "; ".join(m for bit, m in _ERRORS.items() if err & bit))
+    L.raise_error_word("instance_predictions", err, _ERRORS)
     Sf = max(sf, 1)
     if B * Sf >= (1 << 31) - 65536:
         raise ValueError(f"segment_to_full_maps ids too large for a batched grouping (B * (max id + 1) = {B * Sf})")

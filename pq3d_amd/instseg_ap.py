@@ -40,11 +40,9 @@ import torch
 from . import _lib as L
 from .ops import SegmentPlan
 
-INST = 1000              # PQ3D_AP_INST: id = label * 1000 + instance
-MAX_K = 1024             # PQ3D_AP_MAX_K
-MAX_LABELS = 4096        # PQ3D_AP_MAX_LABELS: valid label ids lie in [1, 4096)
-GT_CHUNK = 4096          # PQ3D_INSTSEG_GT_CHUNK
-BOX_PART_BYTES = 64      # PQ3D_INSTSEG_BOX_PART_BYTES
+INST = L.H.PQ3D_AP_INST                       # id = label * INST + instance
+MAX_K, MAX_LABELS = L.H.PQ3D_AP_MAX_K, L.H.PQ3D_AP_MAX_LABELS       # valid label ids lie in [1, MAX_LABELS)
+GT_CHUNK, BOX_PART_BYTES = L.H.PQ3D_INSTSEG_GT_CHUNK, L.H.PQ3D_INSTSEG_BOX_PART_BYTES
 
 
 def default_overlaps() -> np.ndarray:

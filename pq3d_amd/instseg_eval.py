@@ -31,8 +31,7 @@ from . import _lib as L
 from .instseg import instance_predictions
 from .instseg_ap import MAX_K, InstSegAP, gt_boxes, overlap_tables
 
-MAX_G = 4096             # PQ3D_BOX_MAX_G
-MAX_T = 4                # PQ3D_BOX_MAX_T
+MAX_G, MAX_T = L.H.PQ3D_BOX_MAX_G, L.H.PQ3D_BOX_MAX_T
 ERR_NAN_SCORE, ERR_PRED_BOX, ERR_GT_BOX, ERR_OFFSETS = 1, 2, 4, 8
 _ERRORS = {ERR_NAN_SCORE: "a NaN score", ERR_PRED_BOX: "a non-finite prediction box", ERR_GT_BOX: "a non-finite GT box",
            ERR_OFFSETS: "scene offsets out of range"}
@@ -112,8 +111,7 @@ def box_match(pred_records: Sequence[Dict[str, torch.Tensor]], gt_records: Seque
 
 
 def check_errors(err: int, who: str = "box_match") -> None:
-    if err:
-        raise ValueError(f"{who}: " + "; ".join(m for bit, m in _ERRORS.items() if err & bit))
+    L.raise_error_word(who, err, _ERRORS)
 
 
 def voc_ap(rec: np.ndarray, prec: np.ndarray) -> np.float64:

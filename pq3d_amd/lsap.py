@@ -11,8 +11,8 @@ import torch
 
 from . import _lib as L
 
-MAX_DIM = 1024      # PQ3D_LSAP_MAX_DIM: rows and columns of every matrix of a launch
-INVALID, INFEASIBLE, BAD_SIZE = 1, 2, 3      # PQ3D_LSAP_INVALID / _INFEASIBLE / _BAD_SIZE
+MAX_DIM = L.H.PQ3D_LSAP_MAX_DIM      # rows and columns of every matrix of a launch
+INVALID, INFEASIBLE, BAD_SIZE = L.H.PQ3D_LSAP_INVALID, L.H.PQ3D_LSAP_INFEASIBLE, L.H.PQ3D_LSAP_BAD_SIZE
 _MESSAGES = {INVALID: "matrix contains invalid numeric entries", INFEASIBLE: "cost matrix is infeasible",
              BAD_SIZE: "n_rows / n_cols outside [0, R] / [0, Cmax]"}
 

@@ -27,10 +27,8 @@ import torch
 
 from . import _lib as L
 
-MAX_POINTS = 1 << 20        # PQ3D_OBJECT_MAX_POINTS: points per scan
-MAX_ROWS = 1024             # PQ3D_OBJECT_MAX_ROWS: object rows per scan
-CHUNK = 1024                # PQ3D_OBJECT_CHUNK
-MAX_SAMPLE = 4096           # PQ3D_OBJECT_MAX_SAMPLE
+MAX_POINTS, MAX_ROWS = L.H.PQ3D_OBJECT_MAX_POINTS, L.H.PQ3D_OBJECT_MAX_ROWS       # points / object rows per scan
+CHUNK, MAX_SAMPLE = L.H.PQ3D_OBJECT_CHUNK, L.H.PQ3D_OBJECT_MAX_SAMPLE
 _ERRORS = {1: "scene_of_item holds a scan index outside the bank",
            2: "selected holds an object index outside [-1, objects of the item's scan)",
            4: "a sampling cycle walk hit its iteration cap",
@@ -239,8 +237,7 @@ def check_objects(err: torch.Tensor, who: str = "sample_objects") -> None:
     word = 0
     for w in err.reshape(-1).tolist():
         word |= int(w)
-    if word:
-        raise ValueError(f"{who}: " + "; ".join(t for bit, t in _ERRORS.items() if word & bit))
+    L.raise_error_word(who, word, _ERRORS)
 
 
 def ground_labels(bank: ObjectBank, scene_of_item: torch.Tensor, selected: torch.Tensor, targets: torch.Tensor, *,

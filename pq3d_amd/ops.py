@@ -336,7 +336,7 @@ class _MeanAll(Function):
         out = _empty(1, dtype=torch.float32, device=x.device)
         ws = _MEAN_WS.get(x.device)
         if ws is None:     # arrival counter + per-block partials; the kernel leaves the counter at zero again
-            ws = _MEAN_WS[x.device] = torch.zeros(1 + 256, dtype=torch.float32, device=x.device)
+            ws = _MEAN_WS[x.device] = torch.zeros(1 + L.H.PQ3D_MEAN_MAX_BLOCKS, dtype=torch.float32, device=x.device)
         L.call("pq3d_mean_all", x, x.numel(), out, ws)
         ctx.shape = x.shape
         return out.view(())

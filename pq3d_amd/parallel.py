@@ -26,7 +26,7 @@ class NativeComm:
     def __init__(self, rank: int, world: int, unique_id: bytes):
         import ctypes as C
         from . import _lib
-        assert len(unique_id) == 128
+        assert len(unique_id) == _lib.H.PQ3D_COMM_ID_BYTES
         self.rank, self.world = int(rank), int(world)
         self._h = C.c_void_p()
         self._scratch = {}
@@ -36,7 +36,7 @@ class NativeComm:
     def unique_id() -> bytes:
         import ctypes as C
         from . import _lib
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(_lib.H.PQ3D_COMM_ID_BYTES)
         _lib.check(_lib.lib().pq3d_comm_unique_id(buf), "pq3d_comm_unique_id")
         return buf.raw
 

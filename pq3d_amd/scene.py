@@ -34,18 +34,14 @@ import torch
 from . import _lib as L
 from . import collate, ops
 
-MAX_SCENES = 8                 # PQ3D_VOXELIZE_MAX_SCENES (the packed key of sparse._pack has 3 scene bits)
-MAX_POINTS = 1 << 24           # PQ3D_VOXELIZE_MAX_POINTS
-BLOCK = 2048                   # PQ3D_VOXELIZE_BLOCK
-FPS_MAX_SCENES = 64            # PQ3D_FPS_MAX_SCENES
-FPS_MAX_POINTS = 1 << 20       # PQ3D_FPS_MAX_POINTS
+MAX_SCENES = L.H.PQ3D_VOXELIZE_MAX_SCENES            # (the packed key of sparse._pack has 3 scene bits)
+MAX_POINTS, BLOCK = L.H.PQ3D_VOXELIZE_MAX_POINTS, L.H.PQ3D_VOXELIZE_BLOCK
+FPS_MAX_SCENES, FPS_MAX_POINTS = L.H.PQ3D_FPS_MAX_SCENES, L.H.PQ3D_FPS_MAX_POINTS
 _ERRORS = {1: "coordinates hold non-finite values",
            2: "floor(coordinates / voxel_size) leaves [-2^19 + 8, 2^19 - 8)",
            4: "voxel hash table overflow"}
-INSTANCE_MAX_SCENES = 8        # PQ3D_INSTANCE_MAX_SCENES
-INSTANCE_MAX_IDS = 4096        # PQ3D_INSTANCE_MAX_IDS: instance ids lie in [-1, 4096)
-INSTANCE_MAX_FILTER = 16       # PQ3D_INSTANCE_MAX_FILTER
-INSTANCE_MAX_SEGMENTS = 1 << 24   # PQ3D_INSTANCE_MAX_SEGMENTS
+INSTANCE_MAX_SCENES, INSTANCE_MAX_IDS = L.H.PQ3D_INSTANCE_MAX_SCENES, L.H.PQ3D_INSTANCE_MAX_IDS
+INSTANCE_MAX_FILTER, INSTANCE_MAX_SEGMENTS = L.H.PQ3D_INSTANCE_MAX_FILTER, L.H.PQ3D_INSTANCE_MAX_SEGMENTS
 _INSTANCE_ERRORS = {1: f"point2instance holds values outside [-1, {INSTANCE_MAX_IDS})",
                     2: "point2segment holds negative values or values beyond the segment limit (Ns in the padded form)",
                     4: "a scene has more kept instances than max_instances"}
@@ -99,8 +95,7 @@ def voxelize(coordinates: Sequence[torch.Tensor], voxel_size: float):
     meta = torch.empty(B + 2, dtype=torch.int64, device=dev)
     L.call("pq3d_voxelize", pts, C.cast(off, C.c_void_p), B, vs, cap, keys, rep, slot, pv, bsum, unique_map, inverse_map, vcoord, meta)
     m = meta.tolist()                                             # (host sync: outside any graph)
-    if m[B + 1]:
-        raise ValueError("voxelize: " + "; ".join(t for bit, t in _ERRORS.items() if m[B + 1] & bit))
+    L.raise_error_word("voxelize", m[B + 1], _ERRORS)
     vofs = m[:B + 1]
     return (vcoord[:vofs[B]], [unique_map[vofs[b]:vofs[b + 1]] for b in range(B)],
             list(torch.split(inverse_map, lens)))
@@ -165,11 +160,6 @@ def _filter(filter_out_classes) -> Tuple[C.c_void_p, int]:
     return C.cast((C.c_int64 * max(len(f), 1))(*f), C.c_void_p), len(f)
 
 
-def _instance_error(word: int, what: str) -> None:
-    if word:
-        raise ValueError(f"{what}: " + "; ".join(t for bit, t in _INSTANCE_ERRORS.items() if word & bit))
-
-
 class _InstanceTables:
     """First half of ``instance_targets`` (the kernels before the host read): the id tables of a batch and ``meta`` [2 B + 1]
     int32 = kept instances per scene, segments per scene, the error word.  ``masks(meta as a list)`` is the second half."""
@@ -193,7 +183,7 @@ class _InstanceTables:
 
     def masks(self, meta: Sequence[int], with_full_masks: bool) -> Dict[str, list]:
         B, dev = len(self.lens), self.p2i.device
-        _instance_error(meta[2 * B], "instance_targets")
+        L.raise_error_word("instance_targets", meta[2 * B], _INSTANCE_ERRORS)
         G, S = meta[:B], meta[B:2 * B]
         seg_masks = torch.zeros(sum(g * s for g, s in zip(G, S)), dtype=torch.uint8, device=dev)
         full = torch.empty(sum(g * p for g, p in zip(G, self.lens)) if with_full_masks else 0, dtype=torch.uint8, device=dev)
@@ -266,7 +256,7 @@ def padded_instance_targets(point2instance: Sequence[torch.Tensor], point2semant
 
 def check_instance_targets(err: torch.Tensor) -> None:
     """Read the error word of ``padded_instance_targets`` (a host sync) and raise ValueError with the text of its bits."""
-    _instance_error(int(err.reshape(-1)[0]), "padded_instance_targets")
+    L.raise_error_word("padded_instance_targets", int(err.reshape(-1)[0]), _INSTANCE_ERRORS)
 
 
 # ----------------------------------------------------------------------------- train-time augmentation (DESIGN 7e)
@@ -274,7 +264,7 @@ def check_instance_targets(err: torch.Tensor) -> None:
 # {name: (first float, floats)}; this is the only place the Python side spells the layout.
 AUG_FIELDS: Dict[str, Tuple[int, int]] = {n: (getattr(L.SceneAugmentParams, n).offset // 4, getattr(L.SceneAugmentParams, n).size // 4)
                                           for n, *_ in L.SceneAugmentParams._fields_}
-AUG_K = C.sizeof(L.SceneAugmentParams) // 4     # PQ3D_SCENE_AUGMENT_K
+AUG_K = L.H.PQ3D_SCENE_AUGMENT_K
 AUG_STAGES = ("centre", "offset", "flip", "scale", "rotate", "colour")
 COLOR_MEAN = (0.47793125906962, 0.4303257521323044, 0.3749598901421883)      # the reference's A.Normalize constants
 COLOR_STD = (0.2834475483823543, 0.27566157565723015, 0.27018971370874995)
@@ -416,14 +406,9 @@ def augment_scenes(coordinates: Sequence[torch.Tensor], colors: Sequence[torch.T
     return list(torch.split(xyz_out, lens)), list(torch.split(feat_out, lens)), err
 
 
-def _augment_error(word: int, what: str) -> None:
-    if word:
-        raise ValueError(f"{what}: " + "; ".join(t for bit, t in _AUGMENT_ERRORS.items() if word & bit))
-
-
 def check_scene_augment(err: torch.Tensor) -> None:
     """Read the error word of ``augment_scenes`` (a host sync) and raise ValueError with the text of its bits."""
-    _augment_error(int(err.reshape(-1)[0]), "augment_scenes")
+    L.raise_error_word("augment_scenes", int(err.reshape(-1)[0]), _AUGMENT_ERRORS)
 
 
 def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Optional[Sequence[torch.Tensor]],
@@ -520,7 +505,7 @@ def prepare_instseg_batch(coordinates: Sequence[torch.Tensor], features: Optiona
         tops = torch.cat([tops, aug_err.long()])
     tops = tops.tolist()                                         # (host sync)
     if aug_err is not None:
-        _augment_error(tops.pop(), "prepare_instseg_batch")
+        L.raise_error_word("prepare_instseg_batch", tops.pop(), _AUGMENT_ERRORS)
     if derive:
         targets = tables.masks(tops[3 * B:], True)
         instance_ids = targets["instance_ids"]

@@ -33,7 +33,7 @@ import torch.nn as nn
 from . import _lib as L
 from ._lib import BF16, F32
 
-ROW_TILE = 64        # PQ3D_SPARSE_TILE (include/pq3d_hip.h): output rows per workgroup = rows per occupancy word
+ROW_TILE = L.H.PQ3D_SPARSE_TILE        # output rows per workgroup = rows per occupancy word
 _BIAS = 1 << 19      # coordinates (in units of the level's stride) are packed as 20-bit fields
 _ACT = {None: 0, "none": 0, "relu": 1}
 

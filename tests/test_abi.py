@@ -74,6 +74,54 @@ def test_struct_layouts_match_header(tmp_path):
     assert [g for g, w in zip(got, want) if g != w] == [], "header layout (listed) differs from the ctypes Structure"
 
 
+def test_header_constants_match_compiler(tmp_path):
+    """Every non-guard PQ3D_* macro of the header, as gcc evaluates it, against _lib.H: the same names, the same values."""
+    names = [n for n in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PQ3D_\w+)", header_text(), flags=re.M) if n != "PQ3D_HIP_H"]
+    assert len(names) == len(set(names)) >= 56
+    csrc = tmp_path / "constants.c"
+    csrc.write_text('#include <stdio.h>\n#include "pq3d_hip.h"\nint main(void) {\n' +
+                    "\n".join(f'  printf("{n} %lld\\n", (long long)({n}));' for n in names) + "\n  return 0;\n}\n")
+    exe = tmp_path / "constants"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(csrc), "-o", str(exe)])
+    got = {n: int(v) for n, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    assert sorted(got) == sorted(names)
+    assert got == _lib.H._asdict()
+
+
+def test_header_reader_refuses_what_it_cannot_read():
+    for bad in ("1.5f", "(PQ3D_X + 1)", "(1", "1)", "1 + 1", "PQ3D_X"):
+        with pytest.raises(_lib.Pq3dError, match=r"\bPQ3D_BAD\b"):
+            _lib.header_constants(f"#define PQ3D_OK 3\n#define PQ3D_BAD {bad}\n")
+    with pytest.raises(_lib.Pq3dError, match=r"\bPQ3D_BAD\b"):
+        _lib.header_constants("#define PQ3D_BAD(x) 3\n")
+    guard_only = "/* #define PQ3D_A 1 */\n#ifndef PQ3D_X_H\n#define PQ3D_X_H   // #define PQ3D_B 2\n#include <stdint.h>\n#endif\n"
+    assert _lib.header_constants(guard_only)._asdict() == {}
+    text = "#define PQ3D_A ( -0x10 << 2 ) /* a comment\n over two lines */\n  # define PQ3D_B 7 // #define PQ3D_C 1\n#define OTHER x\n"
+    assert _lib.header_constants(text)._asdict() == {"PQ3D_A": -64, "PQ3D_B": 7}
+    with pytest.raises(AttributeError):
+        _lib.H.PQ3D_F32 = 1
+
+
+def test_no_hand_copies_of_header_constants():
+    """No line of the package assigns a numeric literal and names a header macro in a trailing comment."""
+    pat = re.compile(r"=\s*[-(0-9][^#\n]*#\s*PQ3D_[A-Z0-9_]+")
+    assert pat.search("CHUNK = 1024      # PQ3D_OBJECT_CHUNK") and pat.search("MAX_CELLS = (1 << 24)   # PQ3D_DBSCAN_MAX_CELLS: cells")
+    assert not pat.search('    fast = os.environ.get("PQ3D_CHAIN") != "0"      # PQ3D_CHAIN=0: per-sublayer launches')
+    pkg = os.path.join(ROOT, "pq3d_amd")
+    found = [f"{f}: {line.strip()}" for f in sorted(os.listdir(pkg)) if f.endswith(".py")
+             for line in open(os.path.join(pkg, f)) if pat.search(line)]
+    assert found == []
+
+
+def test_error_word_decoder():
+    table = {1: "first", 2: "second", 4: "third", 8: "fourth"}
+    _lib.raise_error_word("who", 0, table)
+    for word, text in ((1 | 4, "who: first; third"), (1 | 8, "who: first; fourth"), (2, "who: second"), (15, "who: first; second; third; fourth")):
+        with pytest.raises(ValueError) as e:
+            _lib.raise_error_word("who", word, table)
+        assert str(e.value) == text and type(e.value) is ValueError
+
+
 def _c_param(decl: str):
     """One parameter of a header prototype -> ('ptr', typedef name or None) | ('int' | 'float', bytes)."""
     words = re.findall(r"\w+", decl.replace("*", " "))[:-1]     # the last word is the parameter's name

@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 import torch
 
+from pq3d_amd.scene import INSTANCE_MAX_IDS as CAP
 from tests import instance_targets_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-CAP = 4096           # PQ3D_INSTANCE_MAX_IDS
 KEYS = ("instance_ids", "instance_labels", "segment_masks", "full_masks")
 
 

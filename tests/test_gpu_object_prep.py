@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 import torch
 
+from pq3d_amd.objects import CHUNK      # points per (row, chunk) cell of the bank build
 from tests import object_prep_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CHUNK = 1024                      # PQ3D_OBJECT_CHUNK: points per (row, chunk) cell of the bank build
 
 
 def _t(a, dtype=None):

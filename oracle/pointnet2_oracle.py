@@ -1,11 +1,16 @@
 """CPU oracle of the PointNet++ point-set operators.  TEST INFRASTRUCTURE ONLY.
 
 numpy restatement of the reference's CUDA kernels (modules/third_party/pointnet2/_ext_src/src/*.cu, file:line on each
-function), written from their behaviour: fp32 arithmetic in the kernels' operation order.  PARITY UNPINNED by execution:
-the reference's extension is CUDA-only (its CPU path is AT_ASSERT(false), ball_query.cpp:28 etc.) and cannot run in the
-build container, and its only test (pointnet2_test.py:18-30) is a gradcheck of three_interpolate at atol 1e-1, which
-tests/test_pointnet2.py repeats.  Tie-breaking of furthest point sampling (duplicated points) follows this file
-(smallest index), not the reference's block-size-dependent reduction tree."""
+function), written from their behaviour: fp32 arithmetic in the kernels' operation order.  PARITY PINNED by execution:
+the reference's extension is GPU-only (its CPU path is AT_ASSERT(false), ball_query.cpp:28 etc.), so
+oracle/build_ref_pointnet2.py builds it for gfx950 and oracle/run_ref_pointnet2.py ran it on an MI355X; its outputs are
+the fixture tests/golden/F18_pointnet2_ref.npz, which tests/test_pointnet2.py holds this file to (every index bit for
+bit, the float outputs to fp32 rounding).  The reference's only own test (pointnet2_test.py:18-30) is a gradcheck of
+three_interpolate at atol 1e-1, which tests/test_pointnet2.py repeats.  Not pinned by the fixture, because its clouds
+have no duplicated points and at least three known points: the tie-breaking of furthest point sampling follows this file
+(smallest index), not the reference's block-size-dependent reduction tree, and three_nn with fewer than three known
+points gives d2 = +inf and index 0 in the missing slots; tests/pointnet2_ref.py restates both from the kernels' contract
+and tests/test_pointnet2_ref.py compares the two."""
 from __future__ import annotations
 
 import numpy as np
@@ -73,8 +78,11 @@ def three_nn(unknown: np.ndarray, known: np.ndarray):
     unknown, known = unknown.astype(np.float32), known.astype(np.float32)
     d = ((unknown[:, :, None, 0] - known[:, None, :, 0]) ** 2 + (unknown[:, :, None, 1] - known[:, None, :, 1]) ** 2
          + (unknown[:, :, None, 2] - known[:, None, :, 2]) ** 2).astype(np.float32)
+    m = d.shape[2]
+    if m < 3:       # the kernel's best2 / best3 keep their 1e40 start (+inf once stored as fp32) and their index 0
+        d = np.concatenate([d, np.full(d.shape[:2] + (3 - m,), np.inf, dtype=np.float32)], 2)
     idx = np.argsort(d, axis=2, kind="stable")[:, :, :3].astype(np.int32)
-    return np.take_along_axis(d, idx, 2), idx
+    return np.take_along_axis(d, idx, 2), np.where(idx < m, idx, 0).astype(np.int32)
 
 
 def three_interpolate(points: np.ndarray, idx: np.ndarray, weight: np.ndarray) -> np.ndarray:
@@ -95,7 +103,7 @@ def pointnetpp_forward(sd, pc: np.ndarray, sa_n_points, sa_n_samples, sa_radii, 
     (pytorch_utils.py:11-36), max over the samples (pointnet2_modules.py:62-65); then fc on the flattened
     [C, npoint] features.  fp64 accumulation in the matmuls is avoided on purpose: fp32 like the reference.
     ``sd``: the module's state_dict as numpy arrays.  The learnable layers of this function ARE pinned (fixture F12 runs
-    the reference's own SharedMLP / fc modules); the point-set operators feeding them are the unpinned ones above."""
+    the reference's own SharedMLP / fc modules); the point-set operators feeding them are the ones above (fixture F18)."""
     pc = pc.astype(np.float32)
     xyz, feats = pc[..., :3], np.transpose(pc[..., 3:], (0, 2, 1)) if pc.shape[-1] > 3 else None     # [B,N,3], [B,C,N]
     for i, (npoint, nsample, radius) in enumerate(zip(sa_n_points, sa_n_samples, sa_radii)):

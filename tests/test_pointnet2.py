@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import pointnet2_oracle as PO
+from tests import pointnet2_ref as REF
 
 DEV = "cuda"
 
@@ -68,23 +69,27 @@ def test_gather_three_nn_and_interpolate_match_oracle():
     dist, idx = P.three_nn(tu, tk)
     d2, ridx = PO.three_nn(unknown, known)
     assert np.array_equal(idx.cpu().numpy(), ridx)
-    assert np.abs(dist.cpu().numpy() - np.sqrt(d2)).max() <= 1e-6
+    assert np.array_equal(dist.cpu().numpy(), np.sqrt(d2))          # fixed-order fp32 (-ffp-contract=off): the same bits
     w = 1.0 / (dist + 1e-8)
     w = (w / w.sum(2, keepdim=True)).contiguous()
     feats = torch.randn(2, 7, 333, device=DEV, requires_grad=True)
     out = P.three_interpolate(feats, idx, w)
     ref = PO.three_interpolate(feats.detach().cpu().numpy(), ridx, w.cpu().numpy())
-    assert np.abs(out.detach().cpu().numpy() - ref).max() <= 1e-5
+    assert np.array_equal(out.detach().cpu().numpy(), ref)
     fidx = P.furthest_point_sample(tk, 50)
     gat = P.gather_operation(feats, fidx)
     assert np.array_equal(gat.detach().cpu().numpy(), PO.gather_points(feats.detach().cpu().numpy(), fidx.cpu().numpy()))
     (out.sum() * 2 + gat.sum() * 3).backward()
-    ref_g = np.zeros((2, 7, 333), dtype=np.float64)
-    for b in range(2):
-        for k in range(3):
-            np.add.at(ref_g[b].T, ridx[b, :, k], np.repeat((2 * w[b, :, k].cpu().numpy())[:, None], 7, 1))
-        np.add.at(ref_g[b].T, fidx[b].cpu().numpy(), 3.0)
-    assert np.abs(feats.grad.cpu().numpy() - ref_g).max() <= 1e-3 * np.abs(ref_g).max()
+    # every element against float64 (tests/pointnet2_ref.py): feats.grad[b, c, j] is the fp32 sum, in some order, of k terms --
+    # 2 w for every (i, slot) with idx == j, each an fp32 product, and 3 for every occurrence of j in fidx -- so it is
+    # within (k + 1) 2^-24 sum|term| of the exact sum; an element with no term is exactly 0
+    wn, fi = w.cpu().numpy(), fidx.cpu().numpy()
+    two, three = np.full((2, 7, 2000), 2.0), np.full((2, 7, 50), 3.0)
+    ref_g = REF.three_interpolate_grad(two, ridx, wn, 2, 7, 333, 2000) + REF.gather_points_grad(three, fi, 2, 7, 333, 50)
+    ref_abs = (REF.three_interpolate_grad_abs(two, ridx, wn, 2, 7, 333, 2000)
+               + REF.gather_points_grad_abs(three, fi, 2, 7, 333, 50))
+    k = REF.three_interpolate_grad_terms(ridx, 2, 333, 2000) + REF.gather_points_grad_terms(fi, 2, 333, 50)
+    assert (np.abs(feats.grad.cpu().numpy() - ref_g) <= (k + 1)[:, None, :] * 2.0 ** -24 * ref_abs).all()
 
 
 @pytest.mark.gpu

@@ -1129,6 +1129,43 @@ int pq3d_group_rows(const float* xyz, const float* new_xyz, const void* feats, i
                     const int32_t* idx, void* out, int32_t dt_o, int32_t B, int32_t N, int32_t C, int32_t np, int32_t ns,
                     int32_t Kp, void* stream);
 int pq3d_group_maxpool(const void* rows, void* out, int32_t dt, int64_t G, int32_t ns, int32_t C, void* stream);
+/* TRAINING the set abstraction (PointNetPP(trainable=True), pq3d_amd/pointnetpp.py; csrc/pointnet2_train.hip): the three steps
+ * of a stage that the kernels above and pq3d_bn_* / pq3d_gemm do not cover.  Rows are fp32, channels last, in pq3d_group_rows'
+ * order (row r = (b np + p) ns + s = g ns + s); G = B np groups of ns samples; mean / rstd are pq3d_bn_stats' over all G ns rows.
+ * No floating-point atomics, every sum in a fixed order (the same bits run to run), no allocation, no synchronisation.
+ *   pq3d_bn_relu_maxpool    forward of a stage's LAST SharedMLP layer from its raw GEMM output z [G ns, ldz]:
+ *                           pooled[g, c] = max_s relu((z[g ns + s, c] - mean[c]) rstd[c] gamma[c] + beta[c]) and arg[g, c] (int32)
+ *                           the LOWEST s that attains it (F.max_pool2d's first maximum; a group whose activations are all <= 0
+ *                           has pooled 0, arg 0).  The normalised rows are never written.  The element expression is the one
+ *                           pq3d_bn_apply evaluates (csrc/bn_row.h), so pooled equals the max over samples of its output bit for bit.
+ *   pq3d_bn_pool_bwd_reduce / pq3d_bn_pool_bwd_apply
+ *                           BatchNorm backward of that layer from the pooled gradient gp [G, C].  The row gradient is implied:
+ *                           g[r, c] = gp[g, c] where s == arg[g, c] and pooled[g, c] > 0, else 0.  reduce: dbeta[c] = sum_r g,
+ *                           dgamma[c] = sum_r g xhat (both WRITTEN; part: pq3d_bn_ws_floats(G ns, C) floats); apply:
+ *                           dz[r, c] = gamma rstd (g - dbeta / N - xhat dgamma / N), N = G ns, every row written.  The bodies, row
+ *                           blocks and lane order are pq3d_bn_bwd_reduce / _apply's with another gradient source: the pair equals
+ *                           the dense pair fed the scattered gradient (and y = the ReLU output) bit for bit.
+ *   pq3d_group_rows_bwd     gradient of pq3d_group_rows with respect to the point features:
+ *                           dfeats[b, j, c] = sum over entries e = (p, s) with idx[b, p, s] == j of drows[(b, p, s), col_off + c],
+ *                           c < C, added in increasing e; a point no entry names gets 0 (as does an index outside [0, N)).
+ *                           drows [B np ns, ldr] (col_off = 3 skips the centred xyz columns, which take no gradient: FPS and
+ *                           ball query are not differentiable and the inputs are data), dfeats [B, N, ldf], every element
+ *                           written.  One workgroup per cloud sorts the np ns entries by source point in LDS (stable counting
+ *                           sort), so N <= PQ3D_GROUP_BWD_MAX_POINTS and np ns <= PQ3D_GROUP_BWD_MAX_ENTRIES (4 N + 2 np ns + 1024
+ *                           bytes of the 160 KB LDS: 97 KB at both caps; entry ids are 16-bit); beyond either the call is refused.
+ *                           idx == NULL (GroupAll: np == 1, ns == N): the strided column copy dfeats[b, j, c] = drows[b N + j, col_off + c]. */
+#define PQ3D_GROUP_BWD_MAX_POINTS 8192
+#define PQ3D_GROUP_BWD_MAX_ENTRIES 32768
+int pq3d_bn_relu_maxpool(const float* z, int64_t ldz, int64_t G, int32_t ns, int32_t C, const float* mean, const float* rstd,
+                         const float* gamma, const float* beta, float* pooled, int32_t* arg, void* stream);
+int pq3d_bn_pool_bwd_reduce(const float* gp, const float* pooled, const int32_t* arg, const float* z, int64_t ldz, int64_t G,
+                            int32_t ns, int32_t C, const float* mean, const float* rstd, float* dgamma, float* dbeta, float* part,
+                            void* stream);
+int pq3d_bn_pool_bwd_apply(const float* gp, const float* pooled, const int32_t* arg, const float* z, int64_t ldz, int64_t G,
+                           int32_t ns, int32_t C, const float* mean, const float* rstd, const float* gamma, const float* dgamma,
+                           const float* dbeta, float* dz, int64_t lddz, void* stream);
+int pq3d_group_rows_bwd(const float* drows, int64_t ldr, int32_t col_off, const int32_t* idx, float* dfeats, int64_t ldf, int32_t B,
+                        int32_t N, int32_t C, int32_t np, int32_t ns, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pieces of the generation head's decoder body (third-party arithmetic: HF transformers

@@ -381,6 +381,11 @@ _SIGS = {
     "pq3d_group_rows": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     "pq3d_group_maxpool": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
+    # training the set abstraction (csrc/pointnet2_train.hip)
+    "pq3d_bn_relu_maxpool": [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 7,
+    "pq3d_bn_pool_bwd_reduce": [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6,
+    "pq3d_bn_pool_bwd_apply": [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p],
+    "pq3d_group_rows_bwd": [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p],
     "pq3d_rmsnorm_fwd": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p],
     "pq3d_rmsnorm_bwd_res": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                              C.c_int32, C.c_int32, C.c_void_p],

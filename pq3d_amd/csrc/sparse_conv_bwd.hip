@@ -20,6 +20,7 @@
 //   pq3d_bn_*               per-channel statistics / normalisation / their backward over the rows of a level: memory-bound
 //                           column reductions in a fixed order (per-block partials, combined in block order) and elementwise
 //                           passes; every row pointer has a leading dimension.
+#include "bn_row.h"
 #include "common.h"
 
 namespace {
@@ -128,16 +129,7 @@ int wgrad_splits(long N_out, int Cin, int Cout, int K, int splits) {
 }
 
 // ---- batch-statistics BatchNorm -----------------------------------------------------------------------------------------
-// Column reductions: block (32 columns x 8 row lanes), grid (P row blocks, ceil(C / 32)).  Row block p owns rows
-// [p rpb, (p + 1) rpb); thread (col, rl) walks rows rl, rl + 8, ... of it; the 8 row lanes are combined in lane order by
-// thread rl = 0; the P partials are combined in block order by the finalize kernel.
-constexpr int BN_CW = 32, BN_RL = 8, BN_MAXP = 256;
-
-__host__ __device__ inline long bn_blocks(long N) {
-  long P = (N + 63) / 64;
-  return P < 1 ? 1 : P > BN_MAXP ? BN_MAXP : P;
-}
-
+// The column-reduction layout, the element expression and the backward bodies are bn_row.h's (shared with pointnet2_train.hip).
 PQ_DEV void chan(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
   if (nb == 0.f) return;
   const float nt = n + nb, dl = mb - mean;
@@ -206,78 +198,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long r = e / C;
     const int c = (int)(e - r * C);
-    float y = (z[r * ldz + c] - mean[c]) * rstd[c] * gamma[c] + beta[c];
+    float y = bn_affine(z[r * ldz + c], mean[c], rstd[c], gamma[c], beta[c]);
     if (residual) y += residual[r * ldr + c];
     if (act == PQ3D_ACT_RELU) y = fmaxf(y, 0.f);
     out[r * ldo + col_off + c] = y;
   }
-}
-
-__global__ __launch_bounds__(BN_CW * BN_RL) void bn_bwd_partial_kernel(const float* __restrict__ dy, long lddy,
-                                                                       const float* __restrict__ y, long ldy,
-                                                                       const float* __restrict__ z, long ldz, long N, int C,
-                                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                       float* __restrict__ part) {
-  __shared__ float sh[2][BN_RL][BN_CW];
-  const int col = threadIdx.x & (BN_CW - 1), rl = threadIdx.x / BN_CW, c = blockIdx.y * BN_CW + col;
-  const long P = gridDim.x, rpb = (N + P - 1) / P, r0 = (long)blockIdx.x * rpb, r1 = r0 + rpb < N ? r0 + rpb : N;
-  float sg = 0.f, sgx = 0.f;
-  if (c < C) {
-    const float m = mean[c], rs = rstd[c];
-    for (long r = r0 + rl; r < r1; r += BN_RL) {
-      float gv = dy[r * lddy + c];
-      if (y && !(y[r * ldy + c] > 0.f)) gv = 0.f;
-      sg += gv;
-      sgx += gv * ((z[r * ldz + c] - m) * rs);
-    }
-  }
-  sh[0][rl][col] = sg; sh[1][rl][col] = sgx;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    for (int j = 1; j < BN_RL; ++j) { sg += sh[0][j][col]; sgx += sh[1][j][col]; }
-    float* p = part + ((long)blockIdx.x * C + c) * 2;
-    p[0] = sg; p[1] = sgx;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ part, int P, int C, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  float sg = 0.f, sgx = 0.f;
-  for (int p = 0; p < P; ++p) {
-    sg += part[((long)p * C + c) * 2];
-    sgx += part[((long)p * C + c) * 2 + 1];
-  }
-  dbeta[c] = sg;
-  dgamma[c] = sgx;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ y,
-                                                           long ldy, const float* __restrict__ z, long ldz, long N, int C,
-                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                           const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                                           const float* __restrict__ dbeta, float* __restrict__ dz, long lddz,
-                                                           float* dres, long lddres, int dres_add) {
-  const long total = N * C;
-  const float inv_n = 1.f / (float)N;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const long r = e / C;
-    const int c = (int)(e - r * C);
-    float gv = dy[r * lddy + c];
-    if (y && !(y[r * ldy + c] > 0.f)) gv = 0.f;
-    const float rs = rstd[c], xh = (z[r * ldz + c] - mean[c]) * rs;
-    dz[r * lddz + c] = gamma[c] * rs * (gv - dbeta[c] * inv_n - xh * (dgamma[c] * inv_n));
-    if (dres) {
-      float* p = dres + r * lddres + c;
-      *p = dres_add ? *p + gv : gv;
-    }
-  }
-}
-
-unsigned ew_grid(long total) {
-  long gsz = (total + 255) / 256;
-  return (unsigned)(gsz > 16384 ? 16384 : gsz < 1 ? 1 : gsz);
 }
 
 }  // namespace
@@ -369,13 +294,8 @@ extern "C" int pq3d_bn_bwd_reduce(const float* dy, int64_t lddy, const float* y,
   BN_COMMON("pq3d_bn_bwd_reduce");
   PQ_CHECK_ARG(dy && z && mean && rstd && dgamma && dbeta && part, "pq3d_bn_bwd_reduce: dy, z, mean, rstd, dgamma, dbeta and part are required");
   PQ_CHECK_ARG(lddy >= C && ldz >= C && (!y || ldy >= C), "pq3d_bn_bwd_reduce: leading dimensions too small");
-  hipStream_t s = (hipStream_t)stream;
-  const long P = bn_blocks((long)N);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((unsigned)P, (unsigned)((C + BN_CW - 1) / BN_CW)), dim3(BN_CW * BN_RL), 0, s, dy,
-                     (long)lddy, y, (long)ldy, z, (long)ldz, (long)N, (int)C, mean, rstd, part);
-  PQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, (const float*)part, (int)P, (int)C,
-                     dgamma, dbeta);
+  const DenseGrad grad = {dy, (long)lddy, y, (long)ldy};
+  bn_bwd_reduce_launch(grad, z, (long)ldz, (long)N, (int)C, mean, rstd, dgamma, dbeta, part, (hipStream_t)stream);
   PQ_LAUNCH_CHECK();
   return 0;
 }
@@ -390,9 +310,9 @@ extern "C" int pq3d_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, 
                "pq3d_bn_bwd_apply: dy, z, mean, rstd, gamma, dgamma, dbeta and dz are required");
   PQ_CHECK_ARG(lddy >= C && ldz >= C && lddz >= C && (!y || ldy >= C) && (!dres || lddres >= C),
                "pq3d_bn_bwd_apply: leading dimensions too small");
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid((long)N * C)), dim3(256), 0, (hipStream_t)stream, dy, (long)lddy, y, (long)ldy,
-                     z, (long)ldz, (long)N, (int)C, mean, rstd, gamma, dgamma, dbeta, dz, (long)lddz, dres, (long)lddres,
-                     (int)dres_add);
+  const DenseGrad grad = {dy, (long)lddy, y, (long)ldy};
+  bn_bwd_apply_launch(grad, z, (long)ldz, (long)N, (int)C, mean, rstd, gamma, dgamma, dbeta, dz, (long)lddz, dres, (long)lddres,
+                      (int)dres_add, (hipStream_t)stream);
   PQ_LAUNCH_CHECK();
   return 0;
 }

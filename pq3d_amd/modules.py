@@ -828,19 +828,26 @@ class T5(_PostNormBase):
 
 # ------------------------------------------------------------------------------------------------ input side
 class ObjectEncoder(_PostNormBase):
-    """modules/vision/object_encoder.py:15-79, projection path (backbone='none')."""
+    """modules/vision/object_encoder.py:15-79: the projection path (backbone='none'), or backbone='pointnet++' -- the frozen
+    tokenizer (freeze_backbone=True), or, with the trailing keyword ``trainable_backbone=True`` and freeze_backbone=False,
+    ``PointNetPP(trainable=True)``: batch statistics and gradients in train(), the frozen path under no_grad in eval()."""
 
     def __init__(self, cfg, backbone="none", input_feat_size=768, hidden_size=768, freeze_backbone=False,
-                 use_projection=False, tgt_cls_num=607, pretrained=None, dropout=0.1, use_cls_head=True):
+                 use_projection=False, tgt_cls_num=607, pretrained=None, dropout=0.1, use_cls_head=True,
+                 trainable_backbone=False):
         super().__init__()
         self.freeze_backbone = freeze_backbone
-        if backbone == "pointnet++":       # object_encoder.py:22-28: the frozen point tokenizer on the HIP kernels
+        if backbone == "pointnet++":       # object_encoder.py:22-28: the point tokenizer on the HIP kernels
             from .pointnetpp import POINTNETPP_TOKENIZER, PointNetPP
-            if not freeze_backbone:
+            if not freeze_backbone and not trainable_backbone:
                 raise NotImplementedError("backbone='pointnet++' is provided as the frozen tokenizer only "
-                                          "(freeze_backbone=True, as configs/unified_tasks_sceneverse.yaml:147-148 uses it)")
+                                          "(freeze_backbone=True, as configs/unified_tasks_sceneverse.yaml:147-148 uses it) unless "
+                                          "trainable_backbone=True asks for the trainable one")
+            # trainable_backbone with freeze_backbone=False: batch-statistics BatchNorm and the set-abstraction backward
+            # (PointNetPP(trainable=True)); with freeze_backbone=True it is the frozen tokenizer, as without the keyword
             self.backbone = PointNetPP(**{k: [list(x) if isinstance(x, list) else x for x in v]
-                                          for k, v in POINTNETPP_TOKENIZER.items()})
+                                          for k, v in POINTNETPP_TOKENIZER.items()},
+                                       trainable=bool(trainable_backbone) and not freeze_backbone)
         elif backbone != "none":
             raise NotImplementedError(f"backbone {backbone!r}")
         if use_cls_head:
@@ -862,14 +869,17 @@ class ObjectEncoder(_PostNormBase):
             self.load_state_dict(state_dict, strict=False)
 
     def forward(self, obj_feats, data_dict=None, **kwargs):
-        if hasattr(self, "backbone"):      # object_encoder.py:56-69: [B, O, P, 3+C] point clouds -> [B, O, 768], frozen
+        if hasattr(self, "backbone"):      # object_encoder.py:56-69: [B, O, P, 3+C] point clouds -> [B, O, 768]
             self.backbone.compute = self.compute
-            for m in self.backbone.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
             B_, O_ = obj_feats.shape[:2]
-            with torch.no_grad():
+            if self.backbone.trainable:    # train(): batch statistics and gradients; eval(): the frozen path under no_grad
                 obj_feats = self.backbone(obj_feats.flatten(0, 1)).view(B_, O_, -1)
+            else:
+                for m in self.backbone.modules():
+                    if isinstance(m, nn.BatchNorm2d):
+                        m.eval()
+                with torch.no_grad():
+                    obj_feats = self.backbone(obj_feats.flatten(0, 1)).view(B_, O_, -1)
         obj_embeds = linear_ln_forward(self.input_feat_proj, obj_feats, self.ct) if self.use_projection else obj_feats
         dev = obj_feats.device
         ctx = self._head_ctx(dev, max(self.dropout_p, self.cls_dropout_p if hasattr(self, "cls_head") else 0.0))

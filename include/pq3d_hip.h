@@ -355,7 +355,7 @@ typedef struct {
   /* backward */
   const float* dy;
   float* dx;                      /* [R,d] fp32 or NULL */
-  float* d_o[PQ3D_MAX_GROUPS];    /* [R,d] fp32 each */
+  float* d_o[PQ3D_MAX_GROUPS];    /* [R,d] each, fp32 (bf16 with dt_d_o) */
   float* dgamma[PQ3D_MAX_GROUPS];
   float* dbeta[PQ3D_MAX_GROUPS];
   int32_t accumulate;             /* != 0: dgamma/dbeta are accumulated onto (not zeroed by the call) */
@@ -375,10 +375,32 @@ typedef struct {
                           already zeroed by the caller -- one zero-fill for a whole backward pass instead of one per call */
   const float* dy2;    /* backward, optional: the upstream gradient is (dy + dy2) + dy3 -- the producers' outputs are summed */
   const float* dy3;    /* here instead of by one more launch (or a dependent "+ aux" chain) in front of this one */
+  int32_t dt_d_o;      /* backward, independent branches only: storage type of d_o (0 = PQ3D_F32; PQ3D_BF16: rounded to nearest even as
+                          the weight-gradient products round their fp32 operands, for consumers that take single-bf16 operands) */
 } pq3d_ln_desc;
 
 int pq3d_add_ln_fwd(const pq3d_ln_desc* d, void* stream);
 int pq3d_add_ln_bwd(const pq3d_ln_desc* d, void* stream);
+
+/* `groups` independent nn.Sequential(Linear, LayerNorm) encoders of one shape in ONE launch (csrc/enc_ln.hip):
+ *     lin_g[R, 256] = x_g[R, K] W_g[256, K]^T + bias_g,     y_g = LayerNorm_g(lin_g),     mean / rstd [groups, R]
+ * -- bit for bit pq3d_gemm at ct PQ3D_BF16X3 followed by pq3d_add_ln_fwd with independent branches and no residual.  fp32,
+ * contiguous rows, N = 256, K in {64, 128, 192, 256}, every pointer 16-byte aligned; bias_g may be NULL.  No workspace, no
+ * synchronisation between workgroups. */
+typedef struct {
+  int32_t R, K, N, groups;
+  float eps;
+  const float* x[PQ3D_MAX_GROUPS];
+  const float* W[PQ3D_MAX_GROUPS];
+  const float* bias[PQ3D_MAX_GROUPS];
+  const float* gamma[PQ3D_MAX_GROUPS];
+  const float* beta[PQ3D_MAX_GROUPS];
+  float* lin[PQ3D_MAX_GROUPS];
+  float* y[PQ3D_MAX_GROUPS];
+  float* mean;
+  float* rstd;
+} pq3d_linear_ln_desc;
+int pq3d_linear_ln_fwd(const pq3d_linear_ln_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The row-local tail of a decoder layer's forward in ONE launch (bf16 mode's split-bf16 query side, ReLU, no dropout):

@@ -179,8 +179,15 @@ class LnDesc(C.Structure):
         ("dbeta", C.c_void_p * MAXG), ("accumulate", C.c_int32), ("independent", C.c_int32),
         ("ys", C.c_void_p * MAXG), ("dys", C.c_void_p * MAXG),
         ("sum_branches", C.c_int32), ("osum", C.c_void_p), ("drop", Dropout), ("dx_zeroed", C.c_int32),
-        ("dy2", C.c_void_p), ("dy3", C.c_void_p),
+        ("dy2", C.c_void_p), ("dy3", C.c_void_p), ("dt_d_o", C.c_int32),
     ]
+
+
+class LinearLnDesc(C.Structure):
+    """pq3d_linear_ln_desc (csrc/enc_ln.hip)."""
+    _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("groups", C.c_int32), ("eps", C.c_float)] + \
+               [(n, C.c_void_p * MAXG) for n in ("x", "W", "bias", "gamma", "beta", "lin", "y")] + \
+               [("mean", C.c_void_p), ("rstd", C.c_void_p)]
 
 
 class ChainFfnDesc(C.Structure):
@@ -284,6 +291,7 @@ _SIGS = {
     "pq3d_cast_transpose": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     "pq3d_add_ln_fwd": [C.POINTER(LnDesc), C.c_void_p],
     "pq3d_add_ln_bwd": [C.POINTER(LnDesc), C.c_void_p],
+    "pq3d_linear_ln_fwd": [C.POINTER(LinearLnDesc), C.c_void_p],
     "pq3d_colsum": [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
     "pq3d_colsum_grouped": [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                             C.c_int64, C.c_int32, C.c_void_p],

@@ -237,7 +237,7 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
     ln_bwd_row(v, dyr, gam, w, mean, rstd, d.d, valid, g, dg, db);
 #pragma unroll
     for (int j = 0; j < PL; ++j) go[j] = drop ? (((keep >> j) & 1u) ? g[j] * dst.scale : 0.f) : g[j];
-    store_row<PL, VEC>(d.d_o[m], PQ3D_F32, base, lane, d.d, go);
+    store_row<PL, VEC>(d.d_o[m], d.dt_d_o, base, lane, d.d, go);   // bf16: what the weight-gradient products round it to anyway
     if (d.dx && !d.independent) {
       if (d.M == 1 || d.sum_branches) store_row<PL, VEC>(d.dx, PQ3D_F32, base, lane, d.d, g);
       else {
@@ -329,6 +329,8 @@ int check_ln(const pq3d_ln_desc& d, bool bwd) {
     PQ_CHECK_ARG(d.o[m] && (!first || (d.gamma[m] && d.beta[m])), "pq3d_add_ln: null o/gamma/beta");
     if (bwd && first) PQ_CHECK_ARG(d.d_o[m] && d.dgamma[m] && d.dbeta[m], "pq3d_add_ln_bwd: null grads");
   }
+  if (bwd) PQ_CHECK_ARG(d.dt_d_o == PQ3D_F32 || (d.dt_d_o == PQ3D_BF16 && d.independent),
+                        "pq3d_add_ln_bwd: bf16 d_o only with independent branches");
   if (bwd) PQ_CHECK_ARG((!d.dy2 && !d.dy3) || (d.dy2 && !d.independent), "pq3d_add_ln_bwd: dy2 / dy3 (dy3 only with dy2; not with independent branches)");
   if (d.independent) {
     for (int m = 0; m < d.M; ++m) PQ_CHECK_ARG(bwd ? d.dys[m] != nullptr : d.ys[m] != nullptr, "pq3d_add_ln: null ys/dys");
@@ -353,7 +355,7 @@ bool ln_vec_ok(const pq3d_ln_desc& d, bool bwd, bool no_dx_atomics = false) {
     ok = ok && al(d.o[m], d.dt_o);
     if (first) ok = ok && al(d.gamma[m], PQ3D_F32) && al(d.beta[m], PQ3D_F32);
     if (d.independent) ok = ok && (bwd ? al(d.dys[m], PQ3D_F32) : al(d.ys[m], d.dt_y));
-    if (bwd && first) ok = ok && al(d.d_o[m], PQ3D_F32);
+    if (bwd && first) ok = ok && al(d.d_o[m], d.dt_d_o);
   }
   if (!d.independent) ok = ok && (bwd ? al(d.dy, PQ3D_F32) && al(d.dx, PQ3D_F32) && al(d.dy2, PQ3D_F32) && al(d.dy3, PQ3D_F32) : al(d.y, d.dt_y));
   return ok && al(d.osum, PQ3D_F32);

@@ -123,7 +123,7 @@ def mlp_head_forward(seq: nn.Sequential, x: torch.Tensor, ct: int, fill_flag=Non
 
 def linear_ln_forward(seq: nn.Sequential, x: torch.Tensor, ct: int) -> torch.Tensor:
     """nn.Sequential(Linear, LayerNorm) as used by the encoders (object_encoder.py:34, query3d_unified.py:20,63-70)."""
-    # the one-encoder case of the grouped Linear+LN op: 2 launches forward; its backward zero-fills every atomics target
+    # the one-encoder case of the grouped Linear+LN op: 1 launch forward at d = 256 (else 2); its backward zero-fills every atomics target
     # (LayerNorm parameter gradients, split-K weight gradient, bias column sums) with ONE fill.
     # 'bf16' mode: split-bf16 forward product.  The encoder outputs (segment features, positions, caption-head input) feed
     # every layer's keys and values, so their operand rounding (1.1e-3 per Linear) would sit under everything downstream:

@@ -956,9 +956,25 @@ def parents_from_coords(fine: torch.Tensor, coarse: torch.Tensor, stride: int) -
 
 
 # ------------------------------------------------------------------------------------------------ grouped Linear + LN
+# PQ3D_ENC_LN=0: the encoders' forward keeps its two launches (grouped GEMM, LayerNorm); PQ3D_ENC_DLIN_BF16=0: their LayerNorm
+# backward hands dlin over in fp32.  For tests and A/B measurements; read once.
+_ENC_LN = os.environ.get("PQ3D_ENC_LN", "1") != "0"
+_ENC_DLIN_BF16 = os.environ.get("PQ3D_ENC_DLIN_BF16", "1") != "0"
+
+
+def _linear_ln_one_launch(ct: int, G: int, R: int, N: int, K: int, xs, params, bs) -> bool:
+    """Is this grouped Linear+LN forward pq3d_linear_ln_fwd's (csrc/enc_ln.hip)?  Split-bf16 products of fp32, contiguous, 16-byte
+    aligned operands into 256 columns over K in {64, 128, 192, 256}; everything else keeps the two launches."""
+    if not _ENC_LN or ct != BF16X3 or N != 256 or K not in (64, 128, 192, 256) or R < 1 or G > L.MAXG:
+        return False
+    if any(b is not None and (b.dtype != torch.float32 or not b.is_contiguous()) for b in bs):
+        return False
+    return all(a.dtype == torch.float32 and a.is_contiguous() and a.data_ptr() % 16 == 0 for a in (*xs, *params))
+
+
 class _LinearLNGroup(Function):
-    """G independent nn.Sequential(Linear, LayerNorm) encoders of identical shape in 2 launches forward
-    (grouped GEMM, independent-branch LayerNorm) and 2 backward (LayerNorm backward, grouped weight-gradient GEMM with
+    """G independent nn.Sequential(Linear, LayerNorm) encoders of identical shape in 1 launch forward (pq3d_linear_ln_fwd; where
+    it does not cover the shape 2: grouped GEMM, independent-branch LayerNorm) and 2 backward (LayerNorm backward, grouped weight-gradient GEMM with
     fused bias gradients) -- ObjectEncoder.input_feat_proj of every scene memory (object_encoder.py:34,71)."""
 
     @staticmethod
@@ -970,18 +986,29 @@ class _LinearLNGroup(Function):
         N = Ws[0].shape[0]
         dev = xs[0].device
         lin = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
-        L.gemm(M=R, N=N, K=K, A=xs, B=[_c(w) for w in Ws], bias=list(bs), Cs=[lin[g] for g in range(G)], ct=ct, lda=K,
-               ldb=K, ldc=N)
         ys = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
         mean = _empty(G, R, dtype=torch.float32, device=dev)
         rstd = torch.empty_like(mean)
-        d = _ln_desc(None, [lin[g] for g in range(G)], [_c(a) for a in gam], [_c(a) for a in bet], None, eps, R, None,
-                     mean, rstd)
-        d.independent = 1
-        d.dt_y = F32
-        for g in range(G):
-            d.ys[g] = L.ptr(ys[g])
-        L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 2.0 * G * R * N * 4))
+        if _linear_ln_one_launch(ct, G, R, N, K, t[:G], (*Ws, *gam, *bet), bs):
+            # one launch (csrc/enc_ln.hip): the LayerNorm runs on the GEMM's row tile, same bits and the same tape.  The test is
+            # on the x the caller gave (t[:G]), not on the contiguous copies in xs: a strided x keeps the two launches
+            d = L.LinearLnDesc()
+            d.R, d.K, d.N, d.groups, d.eps = R, K, N, G, eps
+            d.mean, d.rstd = L.ptr(mean), L.ptr(rstd)
+            for g in range(G):
+                d.x[g], d.W[g], d.bias[g], d.gamma[g], d.beta[g] = L.ptr(xs[g]), L.ptr(Ws[g]), L.ptr(bs[g]), L.ptr(gam[g]), L.ptr(bet[g])
+                d.lin[g], d.y[g] = L.ptr(lin[g]), L.ptr(ys[g])
+            L.call("pq3d_linear_ln_fwd", d, work=(f"R{R}N{N}K{K}g{G}", 6.0 * G * R * N * K, 4.0 * G * (R * (K + 2 * N) + N * K)))
+        else:
+            L.gemm(M=R, N=N, K=K, A=xs, B=[_c(w) for w in Ws], bias=list(bs), Cs=[lin[g] for g in range(G)], ct=ct, lda=K,
+                   ldb=K, ldc=N)
+            d = _ln_desc(None, [lin[g] for g in range(G)], [_c(a) for a in gam], [_c(a) for a in bet], None, eps, R, None,
+                         mean, rstd)
+            d.independent = 1
+            d.dt_y = F32
+            for g in range(G):
+                d.ys[g] = L.ptr(ys[g])
+            L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 2.0 * G * R * N * 4))
         ctx.save_for_backward(lin, mean, rstd, *xs, *Ws, *gam, *bet)
         ctx.cfg = (ct, eps, G, need_dx)
         ctx.pptr = [a.data_ptr() for a in (*Ws, *bs, *gam, *bet)]   # order of the returned parameter gradients
@@ -999,11 +1026,16 @@ class _LinearLNGroup(Function):
         N = Ws[0].shape[0]
         dev = lin.device
         dys = [(_c(g).float() if g is not None else torch.zeros(lin.shape[1:], device=dev)) for g in dys]
-        dlin = _empty(lin.shape, dtype=torch.float32, device=dev)
+        # dlin's only readers round it to bf16 as they load it (single-bf16 weight-gradient / dx products; with `fuse` the bias
+        # gradient is the column sum the product forms from that bf16 operand): then the LayerNorm backward stores it in bf16 --
+        # the same rounding, half the bytes written and read.  The fp32 colsum(dlin) route keeps fp32.
+        dlin = _empty(lin.shape, dtype=torch.bfloat16 if _ENC_DLIN_BF16 and ct == BF16 else torch.float32, device=dev)
+        fuse = wgrad.colsum_fusable(list(dlin), xs, None, N, K, ct)
+        if not fuse and dlin.dtype != torch.float32:
+            dlin = _empty(lin.shape, dtype=torch.float32, device=dev)
         # every atomics target of this backward (LayerNorm parameter gradients, split-K weight gradients, bias column
         # sums): the parameters' slots of the owner's gradient arena when the decoder's backward offered them for this
         # pass (zeroed by its one launch: no fill here, no pack copy later), else ONE zero-filled buffer of our own
-        fuse = wgrad.colsum_fusable(list(dlin), xs, None, N, K, ct)
         slot, give = arena.take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
         if slot is not None:
             dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
@@ -1018,6 +1050,7 @@ class _LinearLNGroup(Function):
         d = _ln_desc(None, [lin[g] for g in range(G)], list(gam), list(bet), None, eps, R, None, mean, rstd)
         d.independent = 1
         d.accumulate = 1
+        d.dt_d_o = L.dt_of(dlin)
         for g in range(G):
             d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dlin[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
         L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 3.0 * G * R * N * 4))

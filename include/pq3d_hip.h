@@ -138,6 +138,10 @@ typedef struct {
   /* dropout applied to the activated output (site = C viewed as [batch*M, N], site id drop.site + group):
    * FFNLayer's self.dropout(self.activation(self.linear1(x))), query_encoder.py:385.  Not with split-K. */
   pq3d_dropout drop;
+  /* Reduction length of group g, or all zero: K for every group.  Only for the grouped weight-gradient layout on the whole-chunk
+   * kernel (transA and transB, ct PQ3D_BF16, split-K with `accumulate`, no epilogue: csrc/gemm_wktt.hip) -- products of one
+   * [M, N] over different row counts in one launch; K must be the largest of them.  Any other call with Kg set is an error. */
+  int32_t Kg[PQ3D_MAX_GROUPS];
 } pq3d_gemm_desc;
 
 int pq3d_gemm(const pq3d_gemm_desc* d, void* stream);
@@ -377,16 +381,20 @@ typedef struct {
   const float* dy3;    /* here instead of by one more launch (or a dependent "+ aux" chain) in front of this one */
   int32_t dt_d_o;      /* backward, independent branches only: storage type of d_o (0 = PQ3D_F32; PQ3D_BF16: rounded to nearest even as
                           the weight-gradient products round their fp32 operands, for consumers that take single-bf16 operands) */
+  int32_t rows[PQ3D_MAX_GROUPS];   /* backward, independent branches only: rows of branch m (all zero: R for every branch).  When set,
+                                      every rows[m < M] >= 1, o / dys / d_o of branch m hold rows[m] rows, mean / rstd are packed branch
+                                      after branch (branch m starts at rows[0] + .. + rows[m - 1]) and R is ignored */
 } pq3d_ln_desc;
 
 int pq3d_add_ln_fwd(const pq3d_ln_desc* d, void* stream);
 int pq3d_add_ln_bwd(const pq3d_ln_desc* d, void* stream);
 
-/* `groups` independent nn.Sequential(Linear, LayerNorm) encoders of one shape in ONE launch (csrc/enc_ln.hip):
- *     lin_g[R, 256] = x_g[R, K] W_g[256, K]^T + bias_g,     y_g = LayerNorm_g(lin_g),     mean / rstd [groups, R]
- * -- bit for bit pq3d_gemm at ct PQ3D_BF16X3 followed by pq3d_add_ln_fwd with independent branches and no residual.  fp32,
- * contiguous rows, N = 256, K in {64, 128, 192, 256}, every pointer 16-byte aligned; bias_g may be NULL.  No workspace, no
- * synchronisation between workgroups. */
+/* `groups` independent nn.Sequential(Linear, LayerNorm) encoders of one (K, N) in ONE launch (csrc/enc_ln.hip):
+ *     lin_g[R_g, 256] = x_g[R_g, K] W_g[256, K]^T + bias_g,     y_g = LayerNorm_g(lin_g),     mean / rstd [R_0 + .. + R_{groups-1}]
+ * -- bit for bit pq3d_gemm at ct PQ3D_BF16X3 followed by pq3d_add_ln_fwd with independent branches and no residual, group by
+ * group.  R_g = rows[g]; rows all zero: R_g = R for every group (mean / rstd then are [groups, R]).  mean / rstd are packed group
+ * after group: group g starts at R_0 + .. + R_{g-1}.  fp32, contiguous rows, N = 256, K in {64, 128, 192, 256}, every pointer
+ * 16-byte aligned; bias_g may be NULL.  No workspace, no synchronisation between workgroups. */
 typedef struct {
   int32_t R, K, N, groups;
   float eps;
@@ -399,6 +407,7 @@ typedef struct {
   float* y[PQ3D_MAX_GROUPS];
   float* mean;
   float* rstd;
+  int32_t rows[PQ3D_MAX_GROUPS];   /* rows of group g, each >= 1; all zero: R for every group */
 } pq3d_linear_ln_desc;
 int pq3d_linear_ln_fwd(const pq3d_linear_ln_desc* d, void* stream);
 

@@ -143,7 +143,7 @@ class GemmDesc(C.Structure):
         ("bias", C.c_void_p * MAXG), ("C", C.c_void_p * MAXG), ("C2", C.c_void_p * MAXG),
         ("aux", C.c_void_p * MAXG), ("row_mask", C.c_void_p * MAXG), ("colsum", C.c_void_p * MAXG),
         ("row_scale", C.c_void_p), ("row_fill_flag", C.c_void_p), ("mask_out", C.c_void_p),
-        ("drop", Dropout),
+        ("drop", Dropout), ("Kg", C.c_int32 * MAXG),
     ]
 
 
@@ -179,7 +179,7 @@ class LnDesc(C.Structure):
         ("dbeta", C.c_void_p * MAXG), ("accumulate", C.c_int32), ("independent", C.c_int32),
         ("ys", C.c_void_p * MAXG), ("dys", C.c_void_p * MAXG),
         ("sum_branches", C.c_int32), ("osum", C.c_void_p), ("drop", Dropout), ("dx_zeroed", C.c_int32),
-        ("dy2", C.c_void_p), ("dy3", C.c_void_p), ("dt_d_o", C.c_int32),
+        ("dy2", C.c_void_p), ("dy3", C.c_void_p), ("dt_d_o", C.c_int32), ("rows", C.c_int32 * MAXG),
     ]
 
 
@@ -187,7 +187,7 @@ class LinearLnDesc(C.Structure):
     """pq3d_linear_ln_desc (csrc/enc_ln.hip)."""
     _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("groups", C.c_int32), ("eps", C.c_float)] + \
                [(n, C.c_void_p * MAXG) for n in ("x", "W", "bias", "gamma", "beta", "lin", "y")] + \
-               [("mean", C.c_void_p), ("rstd", C.c_void_p)]
+               [("mean", C.c_void_p), ("rstd", C.c_void_p), ("rows", C.c_int32 * MAXG)]
 
 
 class ChainFfnDesc(C.Structure):
@@ -576,8 +576,9 @@ def _fill(arr, tensors: Optional[Sequence[Optional[torch.Tensor]]]):
 def gemm(*, M, N, K, A, B, Cs, ct, lda, ldb, ldc, A2=None, B2=None, bias=None, C2=None, aux=None, row_mask=None,
          transA=False, transB=False, batch=1, strideA=0, strideB=0, strideC=0, act=None, act_grad=None, splitk=1,
          kconcat=0, accumulate=False, alpha=1.0, row_scale=None, row_fill_flag=None, row_fill=0.0,
-         mask_out=None, colsum=None, drop=None) -> None:
-    """kconcat: number of consecutive groups concatenated along K per output (True = all groups)."""
+         mask_out=None, colsum=None, drop=None, Kg=None) -> None:
+    """kconcat: number of consecutive groups concatenated along K per output (True = all groups).  Kg: reduction length per group
+    (grouped weight-gradient products over different row counts, see pq3d_gemm_desc.Kg); K is then their maximum."""
     if kconcat is True:
         kconcat = len(A)
     kconcat = int(kconcat or 0)
@@ -599,6 +600,13 @@ def gemm(*, M, N, K, A, B, Cs, ct, lda, ldb, ldc, A2=None, B2=None, bias=None, C
     _fill(d.C2, C2); _fill(d.aux, aux); _fill(d.row_mask, row_mask); _fill(d.colsum, colsum)
     d.row_scale, d.row_fill_flag, d.mask_out = ptr(row_scale), ptr(row_fill_flag), ptr(mask_out)
     set_drop(d.drop, drop)
+    if Kg is not None:
+        for g, k in enumerate(Kg):
+            d.Kg[g] = k
+        ksum = sum(Kg)
+        call("pq3d_gemm", d, work=(f"M{M}N{N}K{'+'.join(map(str, Kg))}TTs{splitk}ct{ct}", 2.0 * M * N * ksum,
+                                   float(ksum * (M * (2 if d.dtA else 4) + N * (2 if d.dtB else 4)) + len(A) * M * N * 4)))
+        return
     nb = (M * K * (2 if d.dtA else 4) + N * K * (2 if d.dtB else 4)) * len(A) * batch + \
         M * N * (2 if d.dtC else 4) * (len(A) // max(kconcat, 1)) * batch
     key = f"M{M}N{N}K{K}g{len(A)}b{batch}{'T' if transA else 'N'}{'T' if transB else 'N'}" \

@@ -1,10 +1,14 @@
-// One launch for G independent nn.Sequential(Linear, LayerNorm) encoders of one shape (ObjectEncoder.input_feat_proj of every scene
-// memory, CoordinateEncoder.feat_proj: N = 256 outputs, K <= 256 inputs, thousands of rows):
+// One launch for G independent nn.Sequential(Linear, LayerNorm) encoders of one (K, N) (ObjectEncoder.input_feat_proj of every scene
+// memory AND CoordinateEncoder.feat_proj: N = 256 outputs, K <= 256 inputs, thousands of rows, a row count per group):
 //     lin_g = x_g W_g^T + b_g          y_g = LN_g(lin_g)          (lin, mean, rstd kept for the backward pass)
 // Until now a grouped GEMM wrote lin and an independent-branch LayerNorm launch read it straight back.  A workgroup that owns whole
 // rows has the complete row when its tile's products finish, so the LayerNorm runs on the tile in LDS; lin leaves once, for the tape.
 //
-// Plan: persistent workgroups, at most one per CU, each with a contiguous range of 32-row tiles (of the G groups laid end to end).
+// Plan: persistent workgroups, at most one per CU, each with a contiguous range of 32-row tiles: the groups' ceil(rows[g] / 32)
+// tiles laid end to end, every group's tiles starting at its row 0 (so a group's tile boundaries do not depend on its neighbours,
+// and a short launch -- the position encoder's 281 tiles, 25 workgroups with a second round -- rides in a long one: 1049 tiles at
+// config 2, 4-5 per workgroup).  A workgroup finds (group, first row) of a tile with a cursor over the groups' tile counts that
+// only moves forward; mean / rstd are packed group after group.
 // Every row here is streaming work (K = 256: 1 KB in, 2 KB out per row), so the compulsory traffic is the floor; what the two-launch
 // path added on top was W: 256 KB per group, fetched from L2 and split into hi / lo bf16 planes once per ROW TILE (as much conversion
 // work per tile as 8 tiles of x).  Here wave w keeps output columns [32 w, 32 w + 32) of W -- hi and lo MFMA fragments over the
@@ -16,7 +20,8 @@
 // Arithmetic is the two launches' own: split-bf16 product (hi / lo planes of chain_common.h's split_hi_lo = gemm.hip's store_split; per
 // 32-wide k step the terms lo*hi, hi*lo, hi*hi, k ascending, one accumulator per output: gemm.hip's mma_tile_x3), bias added to the
 // accumulator, then add_ln_fwd_kernel<4, true>'s independent-branch row: lane l owns columns 4 l .. 4 l + 3, ln_row.h's statistics.
-// tests/test_gpu_enc_ln.py compares lin, mean, rstd and y bit for bit with the two-launch path.
+// tests/test_gpu_enc_ln.py compares lin, mean, rstd and y bit for bit with the two-launch path, tests/test_gpu_enc_ragged.py a
+// launch over unequal groups with one launch per group.
 #include <atomic>
 
 #include "chain_common.h"
@@ -30,7 +35,7 @@ template <int KS> constexpr size_t enc_lds() { return (size_t)2 * TM * (KS * 32 
 
 // KS: 32-wide k steps (K = 32 KS)
 template <int KS>
-__global__ __launch_bounds__(CT) void linear_ln_fwd_kernel(const pq3d_linear_ln_desc d) {
+__global__ __launch_bounds__(CT) void linear_ln_fwd_kernel(const pq3d_linear_ln_desc d, const int ntiles) {
   constexpr int K = KS * 32, LDA = K + 8, CPR = K / 8;        // 8-float chunks per row
   constexpr int NCH = (TM * CPR + CT - 1) / CT;               // chunks of a row tile per thread
   extern __shared__ __attribute__((aligned(16))) unsigned char enc_smem[];
@@ -39,15 +44,29 @@ __global__ __launch_bounds__(CT) void linear_ln_fwd_kernel(const pq3d_linear_ln_
   float* const Ct = (float*)(Al + TM * LDA);                  // [32][ECL]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
   const int wc = wave * 32;                                   // this wave's output columns
-  const int R = d.R, T = (R + TM - 1) / TM;
-  const long total = (long)T * d.groups;
+  // the groups' ceil(rows[g] / 32) tiles laid end to end (the host filled rows[] and counted them)
+  const long total = ntiles;
   const int t0 = (int)(total * blockIdx.x / gridDim.x), t1 = (int)(total * (blockIdx.x + 1) / gridDim.x);
   if (t0 >= t1) return;
+  // (uniform) a cursor over the groups: g holds tiles [tb, tb + tiles(rows[g])) and statistics rows from so on.  Tiles are visited
+  // in ascending order, so a cursor only ever moves forward: at most `groups` steps in a workgroup's life
+  struct Cur { int g, tb, R; long so; };
+  auto seek = [&](Cur& c, int t) {
+    while (t >= c.tb + (c.R + TM - 1) / TM) {
+      c.tb += (c.R + TM - 1) / TM;
+      c.so += c.R;
+      c.R = d.rows[++c.g];
+    }
+  };
+  Cur ci = {0, 0, d.rows[0], 0};      // of the tile whose rows are being fetched
+  seek(ci, t0);
+  Cur cc = ci;                        // of the tile being computed
 
   float av[NCH][8];
-  auto issue = [&](int t) {           // the tile's x rows (rows past R: clamped duplicates, never stored)
-    const int g = t / T, m0 = (t - g * T) * TM;
-    const float* x = d.x[g];
+  auto issue = [&](int t) {           // the tile's x rows (rows past the group's end: clamped duplicates, never stored)
+    seek(ci, t);
+    const int R = ci.R, m0 = (t - ci.tb) * TM;
+    const float* x = d.x[ci.g];
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int ch = tid + i * CT;
@@ -59,7 +78,8 @@ __global__ __launch_bounds__(CT) void linear_ln_fwd_kernel(const pq3d_linear_ln_
   float bcol[2], gm[4], bt[4];
   int cur = -1;
   for (int t = t0; t < t1; ++t) {
-    const int g = t / T, m0 = (t - g * T) * TM;
+    seek(cc, t);
+    const int g = cc.g, R = cc.R, m0 = (t - cc.tb) * TM;
     if (g != cur) {                   // (uniform) this group's weight fragments, bias and LayerNorm parameters
       cur = g;
       const float* W = d.W[g];
@@ -139,8 +159,8 @@ __global__ __launch_bounds__(CT) void linear_ln_fwd_kernel(const pq3d_linear_ln_
 #pragma unroll
         for (int j = 0; j < 4; ++j) { out[j] = 0.f; out[j] += 1.f * ((v[j] - st.mean) * st.rstd * gm[j] + bt[j]); }
         if (lane == 0) {
-          d.mean[(long)g * R + row] = st.mean;
-          d.rstd[(long)g * R + row] = st.rstd;
+          d.mean[cc.so + row] = st.mean;
+          d.rstd[cc.so + row] = st.rstd;
         }
         *(float4*)(yg + base) = make_float4(out[0], out[1], out[2], out[3]);
       }
@@ -160,13 +180,13 @@ int enc_cus() {   // CUs of the current device (one persistent workgroup each)
   return n;
 }
 
-template <int KS> int enc_launch(const pq3d_linear_ln_desc& d, hipStream_t s) {
+template <int KS> int enc_launch(const pq3d_linear_ln_desc& d, int ntiles, hipStream_t s) {
   static std::atomic<unsigned> done{0};
   auto kern = linear_ln_fwd_kernel<KS>;
   if (int e = pq3d_enable_big_lds(kern, (int)enc_lds<KS>(), done)) { pq3d_set_error(hipGetErrorString((hipError_t)e)); return e; }
-  const long total = (long)((d.R + TM - 1) / TM) * d.groups;
+  const long total = ntiles;
   const long cus = enc_cus();
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(CT), enc_lds<KS>(), s, d);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(CT), enc_lds<KS>(), s, d, ntiles);
   return 0;
 }
 
@@ -175,10 +195,21 @@ template <int KS> int enc_launch(const pq3d_linear_ln_desc& d, hipStream_t s) {
 extern "C" int pq3d_linear_ln_fwd(const pq3d_linear_ln_desc* dp, void* stream) {
   PQ_DEVICE_GUARD(stream, dp ? dp->x[0] : nullptr);
   PQ_CHECK_ARG(dp != nullptr, "pq3d_linear_ln_fwd: null descriptor");
-  const pq3d_linear_ln_desc d = *dp;
+  pq3d_linear_ln_desc d = *dp;
   PQ_CHECK_ARG(d.N == EN && d.K >= 64 && d.K <= 256 && d.K % 64 == 0, "pq3d_linear_ln_fwd: N = 256, K in {64, 128, 192, 256}");
-  PQ_CHECK_ARG(d.groups >= 1 && d.groups <= PQ3D_MAX_GROUPS && d.R >= 1, "pq3d_linear_ln_fwd: 1 <= groups <= PQ3D_MAX_GROUPS, R >= 1");
-  PQ_CHECK_ARG((long)d.R * EN < (1L << 31) && (long)((d.R + TM - 1) / TM) * d.groups < (1L << 30), "pq3d_linear_ln_fwd: too many rows");
+  PQ_CHECK_ARG(d.groups >= 1 && d.groups <= PQ3D_MAX_GROUPS, "pq3d_linear_ln_fwd: 1 <= groups <= PQ3D_MAX_GROUPS");
+  bool ragged = false;
+  for (int g = 0; g < PQ3D_MAX_GROUPS; ++g) ragged = ragged || d.rows[g] != 0;
+  long tiles = 0;
+  for (int g = 0; g < PQ3D_MAX_GROUPS; ++g) {
+    if (g >= d.groups) { PQ_CHECK_ARG(d.rows[g] == 0, "pq3d_linear_ln_fwd: rows set past the last group"); continue; }
+    if (!ragged) d.rows[g] = d.R;     // all zero: R rows in every group
+    PQ_CHECK_ARG(d.rows[g] >= 1, ragged ? "pq3d_linear_ln_fwd: every group's rows >= 1 (or all zero)" : "pq3d_linear_ln_fwd: R >= 1");
+    PQ_CHECK_ARG((long)d.rows[g] * EN < (1L << 31), "pq3d_linear_ln_fwd: too many rows");
+    tiles += (d.rows[g] + TM - 1) / TM;
+  }
+  PQ_CHECK_ARG(tiles < (1L << 30), "pq3d_linear_ln_fwd: too many rows");
+  const int nt = (int)tiles;          // (the kernel reads rows[], never R)
   PQ_CHECK_ARG(d.mean && d.rstd, "pq3d_linear_ln_fwd: null mean / rstd");
   for (int g = 0; g < d.groups; ++g) {
     PQ_CHECK_ARG(d.x[g] && d.W[g] && d.gamma[g] && d.beta[g] && d.lin[g] && d.y[g], "pq3d_linear_ln_fwd: null pointer");
@@ -188,10 +219,10 @@ extern "C" int pq3d_linear_ln_fwd(const pq3d_linear_ln_desc* dp, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   int e = 0;
   switch (d.K / 32) {
-    case 2: e = enc_launch<2>(d, s); break;
-    case 4: e = enc_launch<4>(d, s); break;
-    case 6: e = enc_launch<6>(d, s); break;
-    default: e = enc_launch<8>(d, s); break;
+    case 2: e = enc_launch<2>(d, nt, s); break;
+    case 4: e = enc_launch<4>(d, nt, s); break;
+    case 6: e = enc_launch<6>(d, nt, s); break;
+    default: e = enc_launch<8>(d, nt, s); break;
   }
   if (e) return e;
   PQ_LAUNCH_CHECK();

@@ -603,6 +603,19 @@ extern "C" int pq3d_gemm(const pq3d_gemm_desc* dp, void* stream) {
                "pq3d_gemm: colsum needs a transA/transB, non-batched, non-concatenated split-K GEMM");
   hipStream_t s = (hipStream_t)stream;
   pq3d_kdesc kd = make_kdesc(d);   // the kernels' compact form of the descriptor (common.h)
+  bool kg = false;
+  int kg_err = 0;
+  for (int g = 0; g < PQ3D_MAX_GROUPS; ++g) kg = kg || d.Kg[g] != 0;
+  if (kg) {   // per-group reduction lengths: the whole-chunk weight-gradient kernel's alone (gemm_wktt.hip)
+    for (int g = 0; g < PQ3D_MAX_GROUPS; ++g)
+      PQ_CHECK_ARG(g < d.groups ? (d.Kg[g] >= 1 && d.Kg[g] <= d.K) : d.Kg[g] == 0, "pq3d_gemm: 1 <= Kg[g] <= K for every group, none past the last");
+    PQ_CHECK_ARG(d.accumulate && d.splitk > 1 && d.act_grad != PQ3D_ACT_PLANES && pq3d_gemm_wktt_try(d, kd, s, &kg_err),
+                 "pq3d_gemm: Kg needs an accumulating split-K TT product of gemm_wktt's domain (ct PQ3D_BF16, M, N, lda, ldb "
+                 "multiples of 8, 16-byte aligned operands, no epilogue)");
+    if (kg_err) return kg_err;
+    PQ_LAUNCH_CHECK();
+    return 0;
+  }
   if (d.act_grad == PQ3D_ACT_PLANES) {   // bf16 hi / lo planes of the result: the 128-row-tile kernels' epilogues only
     if (pq3d_gemm_x3p_try(d, kd, s)) {   // pre-split operands (A2 / B2 = residual planes), ct PQ3D_BF16X3: gemm_x3p.hip
       PQ_LAUNCH_CHECK();

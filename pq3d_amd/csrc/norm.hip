@@ -172,7 +172,8 @@ __global__ __launch_bounds__(WPB * 64) void add_ln_fwd_kernel(const pq3d_ln_desc
 
 // Backward: blockIdx.y = branch m; each wave walks rows with a grid stride and keeps the per-lane partial dgamma/dbeta of
 // its columns in registers.  dx (sum over branches) is accumulated with atomics only when M > 1.
-template <int PL, bool VEC, int NW>
+// ROWS: independent branches with row counts of their own (pq3d_ln_desc.rows); every other launch takes the ROWS = false code
+template <int PL, bool VEC, int NW, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc d) {
 #ifndef PQ3D_NO_KARG_PIN
   asm volatile("" ::"s"(d.R), "s"(d.d), "s"(d.M), "s"(d.rows_per_scene), "s"(d.dt_x), "s"(d.dt_o), "s"(d.x), "s"(d.coef), "s"(d.mean),
@@ -189,6 +190,14 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
   const int m = blockIdx.y;
   const long wave_id = (long)blockIdx.x * NW + (threadIdx.x >> 6), nwaves = (long)gridDim.x * NW;
   const long nscene = d.coef ? d.R / d.rows_per_scene : 1;
+  // independent branches with rows of their own: this branch's row count; its statistics start after the earlier branches' rows
+  long rows_m = 0, rows_before = 0;
+  if constexpr (ROWS) {
+    rows_m = d.rows[m];
+    for (int i = 0; i < m; ++i) rows_before += d.rows[i];
+  }
+#define LN_BWD_R (ROWS ? rows_m : d.R)                        /* rows of this branch */
+#define LN_BWD_SO (ROWS ? rows_before : (long)m * d.R)        /* where its mean / rstd start */
   float dg[PL], db[PL], gam[PL];
   load_row<PL, VEC>(d.gamma[m], PQ3D_F32, 0, lane, d.d, gam);
 #pragma unroll
@@ -222,17 +231,17 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
 #pragma unroll
     for (int j = 0; j < PL; ++j) nv[j] = xv[j] + ov[j];
   };
-  if (wave_id < d.R) fetch(wave_id);
-  for (long row = wave_id; row < d.R; row += nwaves) {
+  if (wave_id < LN_BWD_R) fetch(wave_id);
+  for (long row = wave_id; row < LN_BWD_R; row += nwaves) {
     const long base = row * d.d;
     float v[PL], dyr[PL];
 #pragma unroll
     for (int j = 0; j < PL; ++j) { v[j] = nv[j]; dyr[j] = ndy[j]; }
     const unsigned keep = nkeep;
-    const float mean = d.mean[(long)m * d.R + row], rstd = d.rstd[(long)m * d.R + row];
+    const float mean = d.mean[LN_BWD_SO + row], rstd = d.rstd[LN_BWD_SO + row];
     const float w = (d.independent || d.sum_branches) ? 1.f
                     : (d.coef ? d.coef[m * nscene + row / d.rows_per_scene] : 1.f / (float)d.M);
-    if (row + nwaves < d.R) fetch(row + nwaves);
+    if (row + nwaves < LN_BWD_R) fetch(row + nwaves);
     float g[PL], go[PL];
     ln_bwd_row(v, dyr, gam, w, mean, rstd, d.d, valid, g, dg, db);
 #pragma unroll
@@ -250,6 +259,8 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_kernel(const pq3d_ln_desc 
     }
   }
   ln_param_grads_flush<PL, VEC, NW>(red, {dg, db}, {d.dgamma[m], d.dbeta[m]}, d.d);
+#undef LN_BWD_R
+#undef LN_BWD_SO
 }
 
 // Merged-branch backward for the big streaming calls (the cross-attention sublayer of a large batch: M = 3 memories, R in the
@@ -317,7 +328,23 @@ __global__ __launch_bounds__(NW * 64) void add_ln_bwd_merged_kernel(const pq3d_l
   }
 }
 
+// rows[] in use (backward, independent branches): the largest branch, else 0
+int ln_ragged_rows(const pq3d_ln_desc& d) {
+  int mx = 0;
+  for (int m = 0; m < PQ3D_MAX_GROUPS; ++m) mx = d.rows[m] > mx ? d.rows[m] : mx;
+  return mx;
+}
+
 int check_ln(const pq3d_ln_desc& d, bool bwd) {
+  bool ragged = false;
+  for (int m = 0; m < PQ3D_MAX_GROUPS; ++m) ragged = ragged || d.rows[m] != 0;
+  if (ragged) {
+    PQ_CHECK_ARG(bwd && d.independent, "pq3d_add_ln: per-branch rows only in the backward of independent branches");
+    PQ_CHECK_ARG(!d.x && !(d.drop.p > 0.f && d.drop.seed != nullptr), "pq3d_add_ln_bwd: per-branch rows exclude a residual and dropout");
+    for (int m = 0; m < PQ3D_MAX_GROUPS; ++m)
+      PQ_CHECK_ARG(m < d.M ? (d.rows[m] >= 1 && (long)d.rows[m] * d.d < (1L << 31)) : d.rows[m] == 0,
+                   "pq3d_add_ln_bwd: rows[m] >= 1 for every branch (or all zero), none past the last");
+  }
   PQ_CHECK_ARG(d.R >= 0 && d.d >= 1 && d.d <= 64 * MAXPL, "pq3d_add_ln: d must be in [1,2048]");
   PQ_CHECK_ARG(d.M >= 1 && d.M <= PQ3D_MAX_GROUPS, "pq3d_add_ln: M out of range");
   PQ_CHECK_ARG(d.rows_per_scene >= 1 && (d.R % d.rows_per_scene) == 0, "pq3d_add_ln: R % rows_per_scene != 0");
@@ -402,7 +429,9 @@ extern "C" int pq3d_add_ln_fwd(const pq3d_ln_desc* dp, void* stream) {
 extern "C" int pq3d_add_ln_bwd(const pq3d_ln_desc* dp, void* stream) {
   PQ_DEVICE_GUARD(stream, dp ? (dp->x ? dp->x : dp->o[0]) : nullptr);
   PQ_CHECK_ARG(dp != nullptr, "pq3d_add_ln_bwd: null descriptor");
-  const pq3d_ln_desc d = *dp;
+  pq3d_ln_desc d = *dp;
+  const int mx = ln_ragged_rows(d);
+  if (mx) { d.R = mx; d.rows_per_scene = 1; }   // per-branch rows: the grid is sized from the largest branch
   if (int e = check_ln(d, true)) return e;
   hipStream_t s = (hipStream_t)stream;
   // 3-branch merged calls (one dx for all branches): the all-branches-per-wave kernel, no dx atomics, no dx zero-fill
@@ -449,9 +478,15 @@ extern "C" int pq3d_add_ln_bwd(const pq3d_ln_desc* dp, void* stream) {
   const bool vec = ln_vec_ok(d, true);
 #define BWD8(PLV, V) hipLaunchKernelGGL((add_ln_bwd_kernel<PLV, V, 8>), grid, dim3(512), 0, s, d)
 #define BWD4(PLV, V) hipLaunchKernelGGL((add_ln_bwd_kernel<PLV, V, 4>), grid, dim3(256), 0, s, d)
-  if (big) { LN_DISPATCH(BWD8, vec) } else { LN_DISPATCH(BWD4, vec) }
+#define BWD8R(PLV, V) hipLaunchKernelGGL((add_ln_bwd_kernel<PLV, V, 8, true>), grid, dim3(512), 0, s, d)
+#define BWD4R(PLV, V) hipLaunchKernelGGL((add_ln_bwd_kernel<PLV, V, 4, true>), grid, dim3(256), 0, s, d)
+  if (mx) {   // per-branch rows
+    if (big) { LN_DISPATCH(BWD8R, vec) } else { LN_DISPATCH(BWD4R, vec) }
+  } else if (big) { LN_DISPATCH(BWD8, vec) } else { LN_DISPATCH(BWD4, vec) }
 #undef BWD8
 #undef BWD4
+#undef BWD8R
+#undef BWD4R
   PQ_LAUNCH_CHECK();
   return 0;
 }

@@ -178,13 +178,62 @@ class Query3DUnified(nn.Module):
         yq, ys = ops.split_rows(y, B * Nq)
         return yq.view(B, Nq, d), ys.view(B, Ns, d)
 
-    def _encode_scene_memories(self, data_dict):
-        """ObjectEncoder projections of all scene memories; same-shape encoders share grouped launches."""
+    def _scene_memories(self, data_dict):
+        """(names, encoders, inputs, same) of the scene memories: `same` where same-shape ObjectEncoder projections share grouped
+        launches."""
         names = [m for m in self.inputs if m in ("mv", "pc", "voxel") and not (m == "voxel" and not self.use_offline_voxel_fts)]
         encs = [getattr(self, m + "_encoder") for m in names]
         xs = [data_dict[m + "_seg_fts"] for m in names]
         same = len(names) > 1 and all(isinstance(e, M.ObjectEncoder) and e.use_projection and not hasattr(e, "cls_head")
                                       for e in encs) and len({tuple(x.shape) for x in xs}) == 1
+        return names, encs, xs, same
+
+    def _memory_dropout(self, ys, encs):
+        """ObjectEncoder's output dropout (object_encoder.py:72-73), same sites as the per-encoder path."""
+        if not self.training:
+            return list(ys)
+        return [ops.dropout(y, e._drop(e._head_ctx(y.device), ops.DROP_ENC_OUT, y.device)) for y, e in zip(ys, encs)]
+
+    def _encode_merged(self, data_dict, query_locs, coord_min, coord_max):
+        """The position pair (_pos_pair) and the scene memories (_encode_scene_memories) through ONE grouped Linear+LN call: the
+        encoders differ in row count only, and neither side depends on the other.  Returns (query_pos, fts_pos, memories), or None
+        where the two calls stay: a Sequential other than (Linear, LayerNorm) of one (K, N, eps), a shape the one-launch forward
+        does not take, dim_loc > 3, PQ3D_ENC_MERGE=0."""
+        ce = self.coord_encoder
+        if not ops._ENC_MERGE or self.dim_loc != 3 or not hasattr(ce, "feat_proj"):
+            return None
+        names, encs, xs, same = self._scene_memories(data_dict)
+        if not same:
+            return None
+        seqs = [ce.feat_proj] + [e.input_feat_proj for e in encs]
+        if not all(isinstance(q, torch.nn.Sequential) and len(q) == 2 and isinstance(q[0], torch.nn.Linear)
+                   and isinstance(q[1], torch.nn.LayerNorm) for q in seqs):
+            return None
+        lin0, ln0 = seqs[0]
+        if any(q[0].weight.shape != lin0.weight.shape or q[1].eps != ln0.eps or (q[0].bias is None) != (lin0.bias is None)
+               for q in seqs[1:]):
+            return None
+        N, K = lin0.weight.shape
+        seg_locs = data_dict["seg_center"]
+        if any(x.shape[-1] != K or x.numel() == 0 for x in xs) or query_locs.numel() == 0 or seg_locs.numel() == 0 or \
+                ce.pos_enc.gauss_B.shape[1] * 2 != K:
+            return None
+        ct = ops.small_ct(self.ct)
+        params = [q[0].weight for q in seqs] + [q[1].weight for q in seqs] + [q[1].bias for q in seqs]
+        # the test on the memories comes before the Fourier launch; its output (fresh, contiguous, fp32) passes by construction
+        if not ops.linear_ln_ragged_ok(ct, N, K, xs, params, [q[0].bias for q in seqs]):
+            return None
+        B, Nq, Ns, d = query_locs.shape[0], query_locs.shape[1], seg_locs.shape[1], self.hidden_size
+        buf = ops.fourier_pair(query_locs[:, :, :3], seg_locs[:, :, :3], coord_min, coord_max, ce.pos_enc.gauss_B)
+        ys = ops.linear_ln_group([buf] + list(xs), [q[0].weight for q in seqs], [q[0].bias for q in seqs],
+                                 [q[1].weight for q in seqs], [q[1].bias for q in seqs], ct=ct, eps=ln0.eps)
+        yq, yseg = ops.split_rows(ys[0], B * Nq)
+        mem = self._memory_dropout([y.view(*x.shape[:-1], N) for y, x in zip(ys[1:], xs)], encs)
+        return yq.view(B, Nq, d), yseg.view(B, Ns, d), dict(zip(names, mem))
+
+    def _encode_scene_memories(self, data_dict):
+        """ObjectEncoder projections of all scene memories; same-shape encoders share grouped launches."""
+        names, encs, xs, same = self._scene_memories(data_dict)
         if not same:
             out = {}
             for m, e, x in zip(names, encs, xs):
@@ -195,9 +244,7 @@ class Query3DUnified(nn.Module):
         ys = ops.linear_ln_group(xs, [q[0].weight for q in seqs], [q[0].bias for q in seqs],
                                  [q[1].weight for q in seqs], [q[1].bias for q in seqs], ct=ops.small_ct(self.ct),
                                  eps=seqs[0][1].eps)   # split-bf16 in 'bf16' mode: see modules.linear_ln_forward
-        if self.training:   # ObjectEncoder's output dropout (object_encoder.py:72-73), same sites as the per-encoder path
-            ys = [ops.dropout(y, e._drop(e._head_ctx(y.device), ops.DROP_ENC_OUT, y.device)) for y, e in zip(ys, encs)]
-        return dict(zip(names, ys))
+        return dict(zip(names, self._memory_dropout(ys, encs)))
 
     def forward(self, data_dict):
         input_dict = {}
@@ -223,7 +270,10 @@ class Query3DUnified(nn.Module):
             mask = data_dict["query_pad_masks"].logical_not()
         query_locs = data_dict["query_locs"][:, :, :self.dim_loc]
         coord_min, coord_max = data_dict["coord_min"], data_dict["coord_max"]
-        if self.dim_loc > 3:
+        merged = self._encode_merged(data_dict, query_locs, coord_min, coord_max)
+        if merged is not None:
+            query_pos, fts_pos, enc_out = merged
+        elif self.dim_loc > 3:
             query_pos = self._pos(query_locs, coord_min, coord_max)
             # NB dim_loc > 3: the reference adds the box embedding to fts_pos twice (query3d_unified.py:128,131-132)
             fts_pos = self._pos(data_dict["seg_center"], coord_min, coord_max, box_times=2)
@@ -233,7 +283,8 @@ class Query3DUnified(nn.Module):
         if zkey not in self._zeros_cache:      # the learnable-query content starts at zero (query3d_unified.py:121): constant
             self._zeros_cache[zkey] = torch.zeros_like(query_pos)
         input_dict["query"] = (self._zeros_cache[zkey], mask, query_pos)
-        enc_out = self._encode_scene_memories(data_dict)
+        if merged is None:
+            enc_out = self._encode_scene_memories(data_dict)
         for inp in self.inputs:
             if inp == "prompt":
                 if "prompt_feat" in data_dict:   # pre-encoded prompt memory (the text encoder ran outside)

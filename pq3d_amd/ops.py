@@ -957,9 +957,13 @@ def parents_from_coords(fine: torch.Tensor, coarse: torch.Tensor, stride: int) -
 
 # ------------------------------------------------------------------------------------------------ grouped Linear + LN
 # PQ3D_ENC_LN=0: the encoders' forward keeps its two launches (grouped GEMM, LayerNorm); PQ3D_ENC_DLIN_BF16=0: their LayerNorm
-# backward hands dlin over in fp32.  For tests and A/B measurements; read once.
+# backward hands dlin over in fp32; PQ3D_ENC_MERGE=0: the model's position encoder and scene-memory encoders stay two calls
+# of the grouped op (model.Query3DUnified._encode_merged); PQ3D_ENC_WGRAD_MERGE=0: a merged call keeps one weight-gradient launch
+# per class of equal row count (no per-group reduction length).  For tests and A/B measurements; read once.
 _ENC_LN = os.environ.get("PQ3D_ENC_LN", "1") != "0"
 _ENC_DLIN_BF16 = os.environ.get("PQ3D_ENC_DLIN_BF16", "1") != "0"
+_ENC_MERGE = os.environ.get("PQ3D_ENC_MERGE", "1") != "0"
+_ENC_WGRAD_MERGE = os.environ.get("PQ3D_ENC_WGRAD_MERGE", "1") != "0"
 
 
 def _linear_ln_one_launch(ct: int, G: int, R: int, N: int, K: int, xs, params, bs) -> bool:
@@ -972,10 +976,38 @@ def _linear_ln_one_launch(ct: int, G: int, R: int, N: int, K: int, xs, params, b
     return all(a.dtype == torch.float32 and a.is_contiguous() and a.data_ptr() % 16 == 0 for a in (*xs, *params))
 
 
+def linear_ln_ragged_ok(ct: int, N: int, K: int, xs, params, bs) -> bool:
+    """Do encoders with DIFFERENT row counts (one K, N, eps) fit one pq3d_linear_ln_fwd launch?  The one-launch forward has to take
+    the shape, and no input gradient is wanted (dx stays with the grouped GEMM of equal row counts)."""
+    return not any(x.requires_grad for x in xs) and all(x.shape[-1] == K and x.numel() >= K for x in xs) and \
+        _linear_ln_one_launch(ct, len(xs), 1, N, K, xs, params, bs)
+
+
+def _row_classes(Rs):
+    """Groups of equal row count, in order of first appearance: [(R, [group indices])]."""
+    cls = {}
+    for g, r in enumerate(Rs):
+        cls.setdefault(r, []).append(g)
+    return list(cls.items())
+
+
+def _class_buffers(Rs, N: int, dtype, device):
+    """[R_g, N] buffers, one per group: the groups of one row count are slices of one [count, R, N] allocation."""
+    out = [None] * len(Rs)
+    for R, idx in _row_classes(Rs):
+        buf = _empty(len(idx), R, N, dtype=dtype, device=device)
+        for i, g in enumerate(idx):
+            out[g] = buf[i]
+    return out
+
+
 class _LinearLNGroup(Function):
-    """G independent nn.Sequential(Linear, LayerNorm) encoders of identical shape in 1 launch forward (pq3d_linear_ln_fwd; where
+    """G independent nn.Sequential(Linear, LayerNorm) encoders of one (K, N) in 1 launch forward (pq3d_linear_ln_fwd; where
     it does not cover the shape 2: grouped GEMM, independent-branch LayerNorm) and 2 backward (LayerNorm backward, grouped weight-gradient GEMM with
-    fused bias gradients) -- ObjectEncoder.input_feat_proj of every scene memory (object_encoder.py:34,71)."""
+    fused bias gradients) -- ObjectEncoder.input_feat_proj of every scene memory (object_encoder.py:34,71).  Encoders of different
+    row counts (the position encoder next to the scene memories) share the forward and the LayerNorm-backward launch where
+    linear_ln_ragged_ok holds: packed mean / rstd, lin / y / dlin as per-group views of one buffer per class of equal row count, one
+    weight-gradient launch with a reduction length per group (wgrad.ragged_fits) or one per class."""
 
     @staticmethod
     def forward(ctx, ct, eps, G, need_dx, *t):
@@ -985,6 +1017,31 @@ class _LinearLNGroup(Function):
         R = xs[0].numel() // K
         N = Ws[0].shape[0]
         dev = xs[0].device
+        Rs = [x.numel() // K for x in xs]
+        if len(set(Rs)) > 1:
+            if need_dx or not linear_ln_ragged_ok(ct, N, K, t[:G], (*Ws, *gam, *bet), bs):
+                raise ValueError("_LinearLNGroup: unequal row counts need the one-launch forward (ops.linear_ln_group splits the rest)")
+            tot = sum(Rs)
+            # lin and y: one buffer per class of equal row count (the layout of one grouped call per class), per-group views;
+            # mean / rstd: flat, group after group, as the launch packs them
+            lin, ys = _class_buffers(Rs, N, torch.float32, dev), _class_buffers(Rs, N, torch.float32, dev)
+            ys = [ys[g].view(*xs[g].shape[:-1], N) for g in range(G)]
+            mean = _empty(tot, dtype=torch.float32, device=dev)
+            rstd = torch.empty_like(mean)
+            d = L.LinearLnDesc()
+            d.R, d.K, d.N, d.groups, d.eps = 0, K, N, G, eps
+            d.mean, d.rstd = L.ptr(mean), L.ptr(rstd)
+            for g in range(G):
+                d.x[g], d.W[g], d.bias[g], d.gamma[g], d.beta[g] = L.ptr(xs[g]), L.ptr(Ws[g]), L.ptr(bs[g]), L.ptr(gam[g]), L.ptr(bet[g])
+                d.lin[g], d.y[g], d.rows[g] = L.ptr(lin[g]), L.ptr(ys[g]), Rs[g]
+            L.call("pq3d_linear_ln_fwd", d, work=(f"R{'+'.join(map(str, Rs))}N{N}K{K}", 6.0 * tot * N * K,
+                                                  4.0 * (tot * (K + 2 * N) + G * N * K)))
+            ctx.save_for_backward(mean, rstd, *lin, *xs, *Ws, *gam, *bet)
+            ctx.cfg = (ct, eps, G, need_dx)
+            ctx.rows = Rs
+            ctx.pptr = [a.data_ptr() for a in (*Ws, *bs, *gam, *bet)]
+            return tuple(ys)
+        ctx.rows = None
         lin = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
         ys = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
         mean = _empty(G, R, dtype=torch.float32, device=dev)
@@ -1018,6 +1075,8 @@ class _LinearLNGroup(Function):
     def backward(ctx, *dys):
         ct, eps, G, need_dx = ctx.cfg
         ct = bwd_ct(ct)
+        if ctx.rows is not None:
+            return _LinearLNGroup._backward_ragged(ctx, ct, eps, G, dys)
         lin, mean, rstd = ctx.saved_tensors[:3]
         t = ctx.saved_tensors[3:]
         xs, Ws, gam, bet = t[:G], t[G:2 * G], t[2 * G:3 * G], t[3 * G:4 * G]
@@ -1073,10 +1132,73 @@ class _LinearLNGroup(Function):
             return (None, None, None, None, *dxs, *([None] * (4 * G)))
         return (None, None, None, None, *dxs, *dWs, *dbl, *dgs, *dbs)
 
+    @staticmethod
+    def _backward_ragged(ctx, ct, eps, G, dys):
+        """Unequal row counts: the tape of the one-launch forward (packed mean / rstd, a lin view per group).  ONE LayerNorm backward
+        over all groups (per-branch rows), then the weight / bias gradients: one grouped launch with a reduction length per group
+        where wgrad.ragged_fits holds, else as the equal-count op forms them, one launch per class of equal row count."""
+        mean, rstd = ctx.saved_tensors[:2]
+        t = ctx.saved_tensors[2:]
+        lin, xs, gam, bet = t[:G], t[G:2 * G], t[3 * G:4 * G], t[4 * G:5 * G]
+        N, K = lin[0].shape[-1], xs[0].shape[-1]
+        Rs, dev = ctx.rows, mean.device
+        dys = [(_c(dy).float() if dy is not None else torch.zeros(Rs[g], N, device=dev)) for g, dy in enumerate(dys)]
+        dl = _class_buffers(Rs, N, torch.bfloat16 if _ENC_DLIN_BF16 and ct == BF16 else torch.float32, dev)
+        fuse = wgrad.colsum_fusable(dl, xs, None, N, K, ct)
+        if not fuse and dl[0].dtype != torch.float32:
+            dl = _class_buffers(Rs, N, torch.float32, dev)
+        slot, give = arena.take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
+        if slot is not None:
+            dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
+            dWs = [w.view(N, K) for w in dWs]
+        else:
+            give = True
+            zb = torch.zeros(G * (3 * N + N * K), dtype=torch.float32, device=dev)
+            dgs = [zb[g * N:(g + 1) * N] for g in range(G)]
+            dbs = [zb[(G + g) * N:(G + g + 1) * N] for g in range(G)]
+            dbl = [zb[(2 * G + g) * N:(2 * G + g + 1) * N] for g in range(G)]
+            dWs = [zb[3 * G * N + g * N * K:3 * G * N + (g + 1) * N * K].view(N, K) for g in range(G)]
+        d = _ln_desc(None, list(lin), list(gam), list(bet), None, eps, 1, None, mean, rstd)
+        d.independent = 1
+        d.accumulate = 1
+        d.dt_d_o = L.dt_of(dl[0])
+        for g in range(G):
+            d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dl[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
+            d.rows[g] = Rs[g]
+        L.call("pq3d_add_ln_bwd", d, work=(f"R{'+'.join(map(str, Rs))}d{N}i", 0.0, 3.0 * sum(Rs) * N * 4))
+        classes = _row_classes(Rs)
+        if fuse and _ENC_WGRAD_MERGE and len(classes) > 1 and wgrad.ragged_fits(dl, xs, N, K, Rs, ct):
+            # long reductions of different lengths: one grouped split-K launch with a reduction length per group
+            wgrad.launch_ragged(dl, xs, dWs, dbl, Rs)
+            classes = []
+        for R, idx in classes:
+            pick = lambda a: [a[g] for g in idx]
+            probs = [(dl[g], xs[g], None, dWs[g], dbl[g]) for g in idx]
+            if fuse and wgrad.tt_multi_fits(probs, N, K, R, ct):
+                wgrad.tt_multi(probs)
+            else:
+                wgrad.launch(pick(dl), pick(xs), None, pick(dWs), pick(dbl) if fuse else None, ct, wgrad.SPLITK_CAP_LAYER)
+        if not fuse:
+            dbl = [colsum(dl[g].view(Rs[g], N)) for g in range(G)]
+        if not give:
+            return (None, None, None, None, *([None] * (5 * G)))
+        return (None, None, None, None, *([None] * G), *dWs, *dbl, *dgs, *dbs)
+
 
 def linear_ln_group(xs, Ws, bs, gammas, betas, *, ct: int, eps: float = 1e-5):
-    """[LayerNorm_g(x_g @ W_g^T + b_g)] for G same-shape encoders in grouped launches."""
+    """[LayerNorm_g(x_g @ W_g^T + b_g)] for G encoders of one (K, N) in grouped launches.  Equal row counts: one grouped op.  Unequal
+    row counts: still one op where the one-launch forward takes the shape (linear_ln_ragged_ok), else one grouped op per class of
+    equal row count."""
     G = len(xs)
+    K, N = xs[0].shape[-1], Ws[0].shape[0]
+    Rs = [x.numel() // K for x in xs]
+    if len(set(Rs)) > 1 and not linear_ln_ragged_ok(ct, N, K, xs, (*Ws, *gammas, *betas), bs):
+        ys = [None] * G
+        for _r, idx in _row_classes(Rs):
+            pick = lambda a: [a[g] for g in idx]
+            for g, y in zip(idx, linear_ln_group(pick(xs), pick(Ws), pick(bs), pick(gammas), pick(betas), ct=ct, eps=eps)):
+                ys[g] = y
+        return tuple(ys)
     need_dx = any(x.requires_grad for x in xs)
     return _LinearLNGroup.apply(ct, float(eps), G, need_dx, *xs, *Ws, *bs, *gammas, *betas)
 

@@ -132,6 +132,26 @@ def launch(gs, xs, x2s, dws, dbs, ct: int, cap: int, *, min2: bool = True, accum
         _colsum_acc(gs, dbs, R)
 
 
+def ragged_fits(gs, xs, N: int, K: int, Rs, ct: int) -> bool:
+    """Can dW_i[N, K] += g_i^T x_i over DIFFERENT long row counts Rs share one grouped launch (pq3d_gemm_desc.Kg: the whole-chunk
+    kernel with a reduction length per group)?  Only products that the per-class launches would send to that kernel anyway: single-
+    bf16 products of rows too many for pq3d_gemm_tt_multi (R >= 2048) and too few tiles for the 128 x 128-tile kernel."""
+    if ct != BF16 or len(gs) > MAXG or N % 8 or K % 8 or min(Rs) < 2048 or len({t.dtype for t in gs}) > 1 or len({t.dtype for t in xs}) > 1:
+        return False
+    if any(dw_long_path(N, K, r, sum(1 for q in Rs if q == r), ct) for r in set(Rs)):
+        return False
+    if gs[0].dtype == torch.bfloat16 and xs[0].dtype == torch.bfloat16:   # the 128 x 128-tile kernel's operands
+        return False
+    return all(t.dtype in (torch.float32, torch.bfloat16) and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in list(gs) + list(xs))
+
+
+def launch_ragged(gs, xs, dws, dbs, Rs) -> None:
+    """dws[i][N, K] += gs[i]^T xs[i] over Rs[i] rows, dbs[i][N] += column sums of gs[i]: ONE split-K launch (see ragged_fits)."""
+    N, K = dws[0].shape
+    L.gemm(M=N, N=K, K=max(Rs), A=list(gs), B=list(xs), Cs=list(dws), ct=BF16, lda=N, ldb=K, ldc=K, transA=True, transB=True, splitk=2,
+           accumulate=True, colsum=list(dbs), Kg=list(Rs))
+
+
 def tt_multi_ok(g, x, x2, dw, db, N: int, K: int, R: int) -> bool:
     """Can dW[N, K] += g^T (x [+ x2]) (+ db[N] += colsum g) join the one-launch flush (pq3d_gemm_tt_multi)?  Not for long
     reductions (R >= 2048): config 2's 3 encoders of [256 x 256] over 8192 rows measured slower there (k-slices x 256 x 128

@@ -225,8 +225,7 @@ class Query3DUnified(nn.Module):
             return None
         B, Nq, Ns, d = query_locs.shape[0], query_locs.shape[1], seg_locs.shape[1], self.hidden_size
         buf = ops.fourier_pair(query_locs[:, :, :3], seg_locs[:, :, :3], coord_min, coord_max, ce.pos_enc.gauss_B)
-        ys = ops.linear_ln_group([buf] + list(xs), [q[0].weight for q in seqs], [q[0].bias for q in seqs],
-                                 [q[1].weight for q in seqs], [q[1].bias for q in seqs], ct=ct, eps=ln0.eps)
+        ys = ops.linear_ln_seqs([buf] + list(xs), seqs, ct)
         yq, yseg = ops.split_rows(ys[0], B * Nq)
         mem = self._memory_dropout([y.view(*x.shape[:-1], N) for y, x in zip(ys[1:], xs)], encs)
         return yq.view(B, Nq, d), yseg.view(B, Ns, d), dict(zip(names, mem))
@@ -241,9 +240,7 @@ class Query3DUnified(nn.Module):
                 out[m] = r[0] if isinstance(r, tuple) else r
             return out
         seqs = [e.input_feat_proj for e in encs]
-        ys = ops.linear_ln_group(xs, [q[0].weight for q in seqs], [q[0].bias for q in seqs],
-                                 [q[1].weight for q in seqs], [q[1].bias for q in seqs], ct=ops.small_ct(self.ct),
-                                 eps=seqs[0][1].eps)   # split-bf16 in 'bf16' mode: see modules.linear_ln_forward
+        ys = ops.linear_ln_seqs(xs, seqs, ops.small_ct(self.ct))   # split-bf16 in 'bf16' mode: see modules.linear_ln_forward
         return dict(zip(names, self._memory_dropout(ys, encs)))
 
     def forward(self, data_dict):

@@ -129,8 +129,7 @@ def linear_ln_forward(seq: nn.Sequential, x: torch.Tensor, ct: int) -> torch.Ten
     # every layer's keys and values, so their operand rounding (1.1e-3 per Linear) would sit under everything downstream:
     # 3.6e-3 of the final query at config 2 by itself (measured with the oracle's rounding emulation); 3 MFMAs on these
     # B*N_seg x d_in x d products cost ~25 us per step.
-    return ops.linear_ln_group([x], [seq[0].weight], [seq[0].bias], [seq[1].weight], [seq[1].bias], ct=ops.small_ct(ct),
-                               eps=seq[1].eps)[0]
+    return ops.linear_ln_seqs([x], [seq], ops.small_ct(ct))[0]
 
 
 def _xavier(module: nn.Module) -> None:

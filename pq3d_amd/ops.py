@@ -958,12 +958,10 @@ def parents_from_coords(fine: torch.Tensor, coarse: torch.Tensor, stride: int) -
 # ------------------------------------------------------------------------------------------------ grouped Linear + LN
 # PQ3D_ENC_LN=0: the encoders' forward keeps its two launches (grouped GEMM, LayerNorm); PQ3D_ENC_DLIN_BF16=0: their LayerNorm
 # backward hands dlin over in fp32; PQ3D_ENC_MERGE=0: the model's position encoder and scene-memory encoders stay two calls
-# of the grouped op (model.Query3DUnified._encode_merged); PQ3D_ENC_WGRAD_MERGE=0: a merged call keeps one weight-gradient launch
-# per class of equal row count (no per-group reduction length).  For tests and A/B measurements; read once.
+# of the grouped op (model.Query3DUnified._encode_merged).  The tests' comparison baselines and A/B measurements; read once.
 _ENC_LN = os.environ.get("PQ3D_ENC_LN", "1") != "0"
 _ENC_DLIN_BF16 = os.environ.get("PQ3D_ENC_DLIN_BF16", "1") != "0"
 _ENC_MERGE = os.environ.get("PQ3D_ENC_MERGE", "1") != "0"
-_ENC_WGRAD_MERGE = os.environ.get("PQ3D_ENC_WGRAD_MERGE", "1") != "0"
 
 
 def _linear_ln_one_launch(ct: int, G: int, R: int, N: int, K: int, xs, params, bs) -> bool:
@@ -1001,188 +999,137 @@ def _class_buffers(Rs, N: int, dtype, device):
     return out
 
 
+def _linear_ln_fwd_desc(xs, Ws, bs, gam, bet, lin, ys, mean, rstd, Rs, eps) -> L.LinearLnDesc:
+    """pq3d_linear_ln_fwd's descriptor.  rows[] is filled only where the row counts differ: all zero means R rows per group."""
+    d = L.LinearLnDesc()
+    ragged = len(set(Rs)) > 1
+    d.R, d.K, d.N, d.groups, d.eps = 0 if ragged else Rs[0], xs[0].shape[-1], Ws[0].shape[0], len(xs), eps
+    d.mean, d.rstd = L.ptr(mean), L.ptr(rstd)
+    for g in range(len(xs)):
+        d.x[g], d.W[g], d.bias[g], d.gamma[g], d.beta[g] = L.ptr(xs[g]), L.ptr(Ws[g]), L.ptr(bs[g]), L.ptr(gam[g]), L.ptr(bet[g])
+        d.lin[g], d.y[g] = L.ptr(lin[g]), L.ptr(ys[g])
+        if ragged:
+            d.rows[g] = Rs[g]
+    return d
+
+
+def _linear_ln_grad_targets(pptr, G: int, N: int, K: int, fuse: bool, dev):
+    """(dWs, dbl, dgs, dbs, give): every atomics target of the grouped Linear+LN backward (LayerNorm parameter gradients, split-K
+    weight gradients, bias column sums).  The parameters' slots of the owner's gradient arena when the decoder's backward offered
+    them for this pass (zeroed by its one launch: no fill here, no pack copy later), else ONE zero-filled buffer of our own.
+    give False: the slots are ones autograd already holds (second micro-batch / second use), nothing is to be returned."""
+    slot, give = arena.take(pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
+    if slot is not None:
+        return [w.view(N, K) for w in slot[:G]], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:], give
+    zb = torch.zeros(G * (3 * N + N * K), dtype=torch.float32, device=dev)
+    dgs = [zb[g * N:(g + 1) * N] for g in range(G)]
+    dbs = [zb[(G + g) * N:(G + g + 1) * N] for g in range(G)]
+    dbl = [zb[(2 * G + g) * N:(2 * G + g + 1) * N] for g in range(G)]
+    dWs = [zb[3 * G * N + g * N * K:3 * G * N + (g + 1) * N * K].view(N, K) for g in range(G)]
+    return dWs, dbl, dgs, dbs, True
+
+
 class _LinearLNGroup(Function):
-    """G independent nn.Sequential(Linear, LayerNorm) encoders of one (K, N) in 1 launch forward (pq3d_linear_ln_fwd; where
-    it does not cover the shape 2: grouped GEMM, independent-branch LayerNorm) and 2 backward (LayerNorm backward, grouped weight-gradient GEMM with
-    fused bias gradients) -- ObjectEncoder.input_feat_proj of every scene memory (object_encoder.py:34,71).  Encoders of different
-    row counts (the position encoder next to the scene memories) share the forward and the LayerNorm-backward launch where
-    linear_ln_ragged_ok holds: packed mean / rstd, lin / y / dlin as per-group views of one buffer per class of equal row count, one
-    weight-gradient launch with a reduction length per group (wgrad.ragged_fits) or one per class."""
+    """G independent nn.Sequential(Linear, LayerNorm) encoders of one (K, N) in 1 launch forward (pq3d_linear_ln_fwd; where it
+    does not cover the shape 2: grouped GEMM, independent-branch LayerNorm) and 2 backward (LayerNorm backward, grouped
+    weight-gradient GEMM with fused bias gradients) -- ObjectEncoder.input_feat_proj of every scene memory
+    (object_encoder.py:34,71), and the position encoder next to them: the groups may differ in row count where
+    linear_ln_ragged_ok holds and no input gradient is wanted.
+    One tape for every call: (mean, rstd, *lin, *xs, *Ws, *gam, *bet) with mean / rstd flat, group after group, and lin / y / dlin
+    as per-group views of one buffer per class of equal row count (equal rows: ONE [G, R, N] allocation).  The descriptors carry
+    rows[] only where the counts differ.  Weight / bias gradients of unequal counts: one launch with a reduction length per group
+    (wgrad.ragged_fits), else one per class."""
 
     @staticmethod
     def forward(ctx, ct, eps, G, need_dx, *t):
         xs = [_c(a) for a in t[:G]]
         Ws, bs, gam, bet = t[G:2 * G], t[2 * G:3 * G], t[3 * G:4 * G], t[4 * G:5 * G]
-        K = xs[0].shape[-1]
-        R = xs[0].numel() // K
-        N = Ws[0].shape[0]
-        dev = xs[0].device
+        K, N, dev = xs[0].shape[-1], Ws[0].shape[0], xs[0].device
         Rs = [x.numel() // K for x in xs]
-        if len(set(Rs)) > 1:
-            if need_dx or not linear_ln_ragged_ok(ct, N, K, t[:G], (*Ws, *gam, *bet), bs):
-                raise ValueError("_LinearLNGroup: unequal row counts need the one-launch forward (ops.linear_ln_group splits the rest)")
-            tot = sum(Rs)
-            # lin and y: one buffer per class of equal row count (the layout of one grouped call per class), per-group views;
-            # mean / rstd: flat, group after group, as the launch packs them
-            lin, ys = _class_buffers(Rs, N, torch.float32, dev), _class_buffers(Rs, N, torch.float32, dev)
-            ys = [ys[g].view(*xs[g].shape[:-1], N) for g in range(G)]
-            mean = _empty(tot, dtype=torch.float32, device=dev)
-            rstd = torch.empty_like(mean)
-            d = L.LinearLnDesc()
-            d.R, d.K, d.N, d.groups, d.eps = 0, K, N, G, eps
-            d.mean, d.rstd = L.ptr(mean), L.ptr(rstd)
-            for g in range(G):
-                d.x[g], d.W[g], d.bias[g], d.gamma[g], d.beta[g] = L.ptr(xs[g]), L.ptr(Ws[g]), L.ptr(bs[g]), L.ptr(gam[g]), L.ptr(bet[g])
-                d.lin[g], d.y[g], d.rows[g] = L.ptr(lin[g]), L.ptr(ys[g]), Rs[g]
-            L.call("pq3d_linear_ln_fwd", d, work=(f"R{'+'.join(map(str, Rs))}N{N}K{K}", 6.0 * tot * N * K,
-                                                  4.0 * (tot * (K + 2 * N) + G * N * K)))
-            ctx.save_for_backward(mean, rstd, *lin, *xs, *Ws, *gam, *bet)
-            ctx.cfg = (ct, eps, G, need_dx)
-            ctx.rows = Rs
-            ctx.pptr = [a.data_ptr() for a in (*Ws, *bs, *gam, *bet)]
-            return tuple(ys)
-        ctx.rows = None
-        lin = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
-        ys = _empty(G, *xs[0].shape[:-1], N, dtype=torch.float32, device=dev)
-        mean = _empty(G, R, dtype=torch.float32, device=dev)
+        R, tot = Rs[0], sum(Rs)
+        # the test is on the x the caller gave (t[:G]), not on the contiguous copies in xs: a strided x keeps the two launches
+        ragged = len(set(Rs)) > 1
+        par = (*Ws, *gam, *bet)
+        one = linear_ln_ragged_ok(ct, N, K, t[:G], par, bs) if ragged else _linear_ln_one_launch(ct, G, R, N, K, t[:G], par, bs)
+        if ragged and (need_dx or not one):
+            raise ValueError("_LinearLNGroup: unequal row counts need the one-launch forward (ops.linear_ln_group splits the rest)")
+        lin, ys = _class_buffers(Rs, N, torch.float32, dev), _class_buffers(Rs, N, torch.float32, dev)
+        ys = [ys[g].view(*xs[g].shape[:-1], N) for g in range(G)]
+        mean = _empty(tot, dtype=torch.float32, device=dev)
         rstd = torch.empty_like(mean)
-        if _linear_ln_one_launch(ct, G, R, N, K, t[:G], (*Ws, *gam, *bet), bs):
-            # one launch (csrc/enc_ln.hip): the LayerNorm runs on the GEMM's row tile, same bits and the same tape.  The test is
-            # on the x the caller gave (t[:G]), not on the contiguous copies in xs: a strided x keeps the two launches
-            d = L.LinearLnDesc()
-            d.R, d.K, d.N, d.groups, d.eps = R, K, N, G, eps
-            d.mean, d.rstd = L.ptr(mean), L.ptr(rstd)
-            for g in range(G):
-                d.x[g], d.W[g], d.bias[g], d.gamma[g], d.beta[g] = L.ptr(xs[g]), L.ptr(Ws[g]), L.ptr(bs[g]), L.ptr(gam[g]), L.ptr(bet[g])
-                d.lin[g], d.y[g] = L.ptr(lin[g]), L.ptr(ys[g])
-            L.call("pq3d_linear_ln_fwd", d, work=(f"R{R}N{N}K{K}g{G}", 6.0 * G * R * N * K, 4.0 * G * (R * (K + 2 * N) + N * K)))
+        if one:
+            # one launch (csrc/enc_ln.hip): the LayerNorm runs on the GEMM's row tile, same bits and the same tape
+            d = _linear_ln_fwd_desc(xs, Ws, bs, gam, bet, lin, ys, mean, rstd, Rs, eps)
+            key = f"R{'+'.join(map(str, Rs))}N{N}K{K}" if ragged else f"R{R}N{N}K{K}g{G}"
+            L.call("pq3d_linear_ln_fwd", d, work=(key, 6.0 * tot * N * K, 4.0 * (tot * (K + 2 * N) + G * N * K)))
         else:
-            L.gemm(M=R, N=N, K=K, A=xs, B=[_c(w) for w in Ws], bias=list(bs), Cs=[lin[g] for g in range(G)], ct=ct, lda=K,
-                   ldb=K, ldc=N)
-            d = _ln_desc(None, [lin[g] for g in range(G)], [_c(a) for a in gam], [_c(a) for a in bet], None, eps, R, None,
-                         mean, rstd)
+            L.gemm(M=R, N=N, K=K, A=xs, B=[_c(w) for w in Ws], bias=list(bs), Cs=lin, ct=ct, lda=K, ldb=K, ldc=N)
+            d = _ln_desc(None, lin, [_c(a) for a in gam], [_c(a) for a in bet], None, eps, R, None, mean, rstd)
             d.independent = 1
             d.dt_y = F32
             for g in range(G):
                 d.ys[g] = L.ptr(ys[g])
             L.call("pq3d_add_ln_fwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 2.0 * G * R * N * 4))
-        ctx.save_for_backward(lin, mean, rstd, *xs, *Ws, *gam, *bet)
+        ctx.save_for_backward(mean, rstd, *lin, *xs, *Ws, *gam, *bet)
         ctx.cfg = (ct, eps, G, need_dx)
+        ctx.rows = Rs
         ctx.pptr = [a.data_ptr() for a in (*Ws, *bs, *gam, *bet)]   # order of the returned parameter gradients
-        return tuple(ys[g] for g in range(G))
+        return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
         ct, eps, G, need_dx = ctx.cfg
         ct = bwd_ct(ct)
-        if ctx.rows is not None:
-            return _LinearLNGroup._backward_ragged(ctx, ct, eps, G, dys)
-        lin, mean, rstd = ctx.saved_tensors[:3]
-        t = ctx.saved_tensors[3:]
-        xs, Ws, gam, bet = t[:G], t[G:2 * G], t[2 * G:3 * G], t[3 * G:4 * G]
-        K = xs[0].shape[-1]
-        R = xs[0].numel() // K
-        N = Ws[0].shape[0]
-        dev = lin.device
-        dys = [(_c(g).float() if g is not None else torch.zeros(lin.shape[1:], device=dev)) for g in dys]
+        mean, rstd = ctx.saved_tensors[:2]
+        t = ctx.saved_tensors[2:]
+        lin, xs, Ws, gam, bet = t[:G], t[G:2 * G], t[2 * G:3 * G], t[3 * G:4 * G], t[4 * G:5 * G]
+        N, K = lin[0].shape[-1], xs[0].shape[-1]
+        Rs, dev = ctx.rows, mean.device
+        classes = _row_classes(Rs)
+        ragged = len(classes) > 1
+        dys = [(_c(dy).float() if dy is not None else torch.zeros(Rs[g], N, device=dev)) for g, dy in enumerate(dys)]
         # dlin's only readers round it to bf16 as they load it (single-bf16 weight-gradient / dx products; with `fuse` the bias
         # gradient is the column sum the product forms from that bf16 operand): then the LayerNorm backward stores it in bf16 --
         # the same rounding, half the bytes written and read.  The fp32 colsum(dlin) route keeps fp32.
-        dlin = _empty(lin.shape, dtype=torch.bfloat16 if _ENC_DLIN_BF16 and ct == BF16 else torch.float32, device=dev)
-        fuse = wgrad.colsum_fusable(list(dlin), xs, None, N, K, ct)
-        if not fuse and dlin.dtype != torch.float32:
-            dlin = _empty(lin.shape, dtype=torch.float32, device=dev)
-        # every atomics target of this backward (LayerNorm parameter gradients, split-K weight gradients, bias column
-        # sums): the parameters' slots of the owner's gradient arena when the decoder's backward offered them for this
-        # pass (zeroed by its one launch: no fill here, no pack copy later), else ONE zero-filled buffer of our own
-        slot, give = arena.take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
-        if slot is not None:
-            dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
-            dWs = [w.view(N, K) for w in dWs]
-        else:
-            give = True
-            zb = torch.zeros(G * (3 * N + N * K), dtype=torch.float32, device=dev)
-            dgs = [zb[g * N:(g + 1) * N] for g in range(G)]
-            dbs = [zb[(G + g) * N:(G + g + 1) * N] for g in range(G)]
-            dbl = [zb[(2 * G + g) * N:(2 * G + g + 1) * N] for g in range(G)]
-            dWs = [zb[3 * G * N + g * N * K:3 * G * N + (g + 1) * N * K].view(N, K) for g in range(G)]
-        d = _ln_desc(None, [lin[g] for g in range(G)], list(gam), list(bet), None, eps, R, None, mean, rstd)
-        d.independent = 1
-        d.accumulate = 1
-        d.dt_d_o = L.dt_of(dlin)
-        for g in range(G):
-            d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dlin[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
-        L.call("pq3d_add_ln_bwd", d, work=(f"R{R}d{N}M{G}i", 0.0, 3.0 * G * R * N * 4))
-        probs = [(dlin[g], xs[g], None, dWs[g], dbl[g]) for g in range(G)]
-        if fuse and wgrad.tt_multi_fits(probs, N, K, R, ct):
-            # short reductions only: the encoders of small batches / short memories -- one launch with the fused bias gradient,
-            # without the tt_multi_pays check of a queue flush (tests/test_gpu_ops.py::test_linear_ln_group_backward_tt_multi_path)
-            wgrad.tt_multi(probs)
-        else:
-            wgrad.launch([dlin[g] for g in range(G)], list(xs), None, dWs, dbl if fuse else None, ct, wgrad.SPLITK_CAP_LAYER)
-        if not fuse:
-            dbl = [colsum(dlin[g].view(R, N)) for g in range(G)]
-        dxs = [None] * G
-        if need_dx:
-            dxb = _empty(G, *xs[0].shape, dtype=xs[0].dtype, device=dev)
-            L.gemm(M=R, N=K, K=N, A=[dlin[g] for g in range(G)], B=list(Ws), Cs=[dxb[g] for g in range(G)], ct=ct,
-                   lda=N, ldb=K, ldc=K, transB=True)
-            dxs = [dxb[g] for g in range(G)]
-        if not give:   # accumulated in place into slots autograd already holds (second micro-batch / second use)
-            return (None, None, None, None, *dxs, *([None] * (4 * G)))
-        return (None, None, None, None, *dxs, *dWs, *dbl, *dgs, *dbs)
-
-    @staticmethod
-    def _backward_ragged(ctx, ct, eps, G, dys):
-        """Unequal row counts: the tape of the one-launch forward (packed mean / rstd, a lin view per group).  ONE LayerNorm backward
-        over all groups (per-branch rows), then the weight / bias gradients: one grouped launch with a reduction length per group
-        where wgrad.ragged_fits holds, else as the equal-count op forms them, one launch per class of equal row count."""
-        mean, rstd = ctx.saved_tensors[:2]
-        t = ctx.saved_tensors[2:]
-        lin, xs, gam, bet = t[:G], t[G:2 * G], t[3 * G:4 * G], t[4 * G:5 * G]
-        N, K = lin[0].shape[-1], xs[0].shape[-1]
-        Rs, dev = ctx.rows, mean.device
-        dys = [(_c(dy).float() if dy is not None else torch.zeros(Rs[g], N, device=dev)) for g, dy in enumerate(dys)]
         dl = _class_buffers(Rs, N, torch.bfloat16 if _ENC_DLIN_BF16 and ct == BF16 else torch.float32, dev)
         fuse = wgrad.colsum_fusable(dl, xs, None, N, K, ct)
         if not fuse and dl[0].dtype != torch.float32:
             dl = _class_buffers(Rs, N, torch.float32, dev)
-        slot, give = arena.take(ctx.pptr, [N * K] * G + [N] * (3 * G)) if fuse else (None, False)
-        if slot is not None:
-            dWs, dbl, dgs, dbs = slot[:G], slot[G:2 * G], slot[2 * G:3 * G], slot[3 * G:]
-            dWs = [w.view(N, K) for w in dWs]
-        else:
-            give = True
-            zb = torch.zeros(G * (3 * N + N * K), dtype=torch.float32, device=dev)
-            dgs = [zb[g * N:(g + 1) * N] for g in range(G)]
-            dbs = [zb[(G + g) * N:(G + g + 1) * N] for g in range(G)]
-            dbl = [zb[(2 * G + g) * N:(2 * G + g + 1) * N] for g in range(G)]
-            dWs = [zb[3 * G * N + g * N * K:3 * G * N + (g + 1) * N * K].view(N, K) for g in range(G)]
-        d = _ln_desc(None, list(lin), list(gam), list(bet), None, eps, 1, None, mean, rstd)
+        dWs, dbl, dgs, dbs, give = _linear_ln_grad_targets(ctx.pptr, G, N, K, fuse, dev)
+        # ONE LayerNorm backward over all groups; per-branch rows only where the counts differ (a kernel instantiation of its own)
+        d = _ln_desc(None, list(lin), list(gam), list(bet), None, eps, 1 if ragged else Rs[0], None, mean, rstd)
         d.independent = 1
         d.accumulate = 1
         d.dt_d_o = L.dt_of(dl[0])
         for g in range(G):
             d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dl[g]), L.ptr(dgs[g]), L.ptr(dbs[g])
-            d.rows[g] = Rs[g]
-        L.call("pq3d_add_ln_bwd", d, work=(f"R{'+'.join(map(str, Rs))}d{N}i", 0.0, 3.0 * sum(Rs) * N * 4))
-        classes = _row_classes(Rs)
-        if fuse and _ENC_WGRAD_MERGE and len(classes) > 1 and wgrad.ragged_fits(dl, xs, N, K, Rs, ct):
+            if ragged:
+                d.rows[g] = Rs[g]
+        key = f"R{'+'.join(map(str, Rs))}d{N}i" if ragged else f"R{Rs[0]}d{N}M{G}i"
+        L.call("pq3d_add_ln_bwd", d, work=(key, 0.0, 3.0 * sum(Rs) * N * 4))
+        if ragged and fuse and wgrad.ragged_fits(dl, xs, N, K, Rs, ct):
             # long reductions of different lengths: one grouped split-K launch with a reduction length per group
             wgrad.launch_ragged(dl, xs, dWs, dbl, Rs)
             classes = []
-        for R, idx in classes:
+        for R, idx in classes:   # one launch per class of equal row count, in order of first appearance
             pick = lambda a: [a[g] for g in idx]
             probs = [(dl[g], xs[g], None, dWs[g], dbl[g]) for g in idx]
             if fuse and wgrad.tt_multi_fits(probs, N, K, R, ct):
+                # short reductions only: the encoders of small batches / short memories -- one launch with the fused bias gradient,
+                # without the tt_multi_pays check of a queue flush (tests/test_gpu_ops.py::test_linear_ln_group_backward_tt_multi_path)
                 wgrad.tt_multi(probs)
             else:
                 wgrad.launch(pick(dl), pick(xs), None, pick(dWs), pick(dbl) if fuse else None, ct, wgrad.SPLITK_CAP_LAYER)
         if not fuse:
-            dbl = [colsum(dl[g].view(Rs[g], N)) for g in range(G)]
-        if not give:
-            return (None, None, None, None, *([None] * (5 * G)))
-        return (None, None, None, None, *([None] * G), *dWs, *dbl, *dgs, *dbs)
+            dbl = [colsum(dl[g]) for g in range(G)]
+        dxs = [None] * G
+        if need_dx:   # equal row counts: the forward refuses the others
+            dxb = _empty(G, *xs[0].shape, dtype=xs[0].dtype, device=dev)
+            L.gemm(M=Rs[0], N=K, K=N, A=dl, B=list(Ws), Cs=[dxb[g] for g in range(G)], ct=ct, lda=N, ldb=K, ldc=K, transB=True)
+            dxs = [dxb[g] for g in range(G)]
+        if not give:   # accumulated in place into slots autograd already holds (second micro-batch / second use)
+            return (None, None, None, None, *dxs, *([None] * (4 * G)))
+        return (None, None, None, None, *dxs, *dWs, *dbl, *dgs, *dbs)
 
 
 def linear_ln_group(xs, Ws, bs, gammas, betas, *, ct: int, eps: float = 1e-5):
@@ -1201,6 +1148,12 @@ def linear_ln_group(xs, Ws, bs, gammas, betas, *, ct: int, eps: float = 1e-5):
         return tuple(ys)
     need_dx = any(x.requires_grad for x in xs)
     return _LinearLNGroup.apply(ct, float(eps), G, need_dx, *xs, *Ws, *bs, *gammas, *betas)
+
+
+def linear_ln_seqs(xs, seqs, ct: int):
+    """linear_ln_group with x_g through seqs[g], each an nn.Sequential(Linear, LayerNorm); eps is the first LayerNorm's."""
+    return linear_ln_group(xs, [q[0].weight for q in seqs], [q[0].bias for q in seqs], [q[1].weight for q in seqs],
+                           [q[1].bias for q in seqs], ct=ct, eps=seqs[0][1].eps)
 
 
 class _SplitRows(Function):

@@ -6,30 +6,16 @@ import torch
 from pq3d_amd import _lib as L
 from pq3d_amd import ops
 from pq3d_amd._lib import BF16, BF16X3, F32
+from tests.enc_common import DEV, N, _bits_equal, _count_calls, _order_bound, _params, rnd
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-N = 256
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed + sum(shape))
-    return (torch.randn(*shape, generator=g) * scale).float()
 
 
 class _Tape:
-    """Stand-in for the autograd context of _LinearLNGroup.forward: keeps what the op saves (lin, mean, rstd first)."""
+    """Stand-in for the autograd context of _LinearLNGroup.forward: keeps what the op saves (mean, rstd, then lin of every group first)."""
 
     def save_for_backward(self, *ts):
         self.saved = ts
-
-
-def _params(G, K, n=N):
-    Ws = [rnd(n, K, seed=50 + g, scale=0.06).to(DEV) for g in range(G)]
-    bs = [rnd(n, seed=60 + g, scale=0.1).to(DEV) for g in range(G)]
-    gs = [(1 + rnd(n, seed=70 + g, scale=0.1)).to(DEV) for g in range(G)]
-    be = [rnd(n, seed=80 + g, scale=0.1).to(DEV) for g in range(G)]
-    return Ws, bs, gs, be
 
 
 def _inputs(G, R, K):
@@ -47,23 +33,9 @@ def _inputs(G, R, K):
 def _forward(xs, Ws, bs, gs, be, ct=BF16X3):
     tape = _Tape()
     ys = ops._LinearLNGroup.forward(tape, ct, 1e-5, len(xs), False, *xs, *Ws, *bs, *gs, *be)
-    lin, mean, rstd = tape.saved[:3]
-    return ys, lin, mean, rstd
-
-
-def _count_calls(monkeypatch):
-    seen = []
-    real = L.call
-
-    def spy(name, *a, **kw):
-        seen.append(name)
-        return real(name, *a, **kw)
-    monkeypatch.setattr(L, "call", spy)
-    return seen
-
-
-def _bits_equal(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+    G, R = len(xs), xs[0].shape[0]
+    mean, rstd = tape.saved[:2]   # flat, group after group; then one lin [R, N] per group
+    return ys, torch.stack(tape.saved[2:2 + G]), mean.view(G, R), rstd.view(G, R)
 
 
 @pytest.mark.parametrize("K", [64, 256])
@@ -185,12 +157,6 @@ def _ln_bwd(lin, mean, rstd, gs, be, dys, dtype):
         d.dys[g], d.d_o[g], d.dgamma[g], d.dbeta[g] = L.ptr(dys[g]), L.ptr(dlin[g]), L.ptr(dg[g]), L.ptr(db[g])
     L.call("pq3d_add_ln_bwd", d)
     return dlin, dg, db
-
-
-def _order_bound(contrib_abs, terms):
-    """Largest difference between two fp32 sums of the same `terms` addends taken in different orders: each order is within
-    (terms - 1) 2^-24 sum|addend| of the exact sum (first-order bound of recursive summation), so two orders are within twice that."""
-    return 2.0 * max(terms - 1, 1) * 2.0 ** -24 * contrib_abs
 
 
 @pytest.mark.parametrize("R", [1, 33, 300])
